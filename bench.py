@@ -10,7 +10,22 @@ full backward -> RCCL all-reduce of the flat gradient -> clip + SGD.
 Throughput = roots processed by all ranks / max-over-ranks wall time of the
 timed steps (weak scaling: B roots per GPU per step).
 
-Prints ONE JSON line on rank 0.  `roofline` prices the dominant kernel (the
+Prints ONE JSON line on rank 0.  A plain run does what the headline figure
+needs and nothing more: set-up, warmup, the cold window that fills the sampler
+pipeline, the --steps timed steps of the steady window (`value`,
+`ms_per_step`), the --dump-outputs files, the line.  Everything else runs only
+with --full: the kernel timers inside and after the timed steps (`roofline`,
+`roofline_kernels`), the `sustained` and `reference_stream` windows, the
+sampled-node replay (`sampled_nodes_per_s`) and `cpu_baseline`.
+
+--dump-outputs DIR writes what the timed path left after its last timed step
+as DIR/<name>.npy (float32): the step's loss and every parameter after its
+update for the training configs, the embeddings for rmat2m-embed (a seeded row
+sample above 64 MB in all).  Graph, features, weights, batches and sampler
+streams are seeded, so the same arguments on the same host layout give the same
+inputs and two builds can be compared file by file.
+
+With --full, `roofline` prices the dominant kernel (the
 largest average in the committed rocprofv3 summary of the config: the layer-1
 forward GEMM at fp32, the dW GEMM at bf16) from its algorithmic flops or bytes
 against the peak of the MFMA it issues (the bf16 dW widens its operands to
@@ -80,6 +95,8 @@ SITE_ROLES = {0: "layer-1 gather-aggregate (models.py:291-330 at layer 1)",
               3: "top layer + loss head in one launch: layer-2 aggregate, linear + relu, log_softmax/NLL, dZ2, "
                  "dIn2 = dZ2·W2 (models.py:291-330, :216-219, :8-27; utils.py:159-164)"}
 MFMA_PEAK_TFS = {"fp32": 157.3, "bf16": 2500.0}  # MI355X_MICROARCH.md: dense F32 / BF16 matrix peaks (spec)
+# a plain run's longest cold window: several times the default sampler pipeline (12 streams x 4 slots)
+FILL_STEPS = 256
 
 
 def host_cores():
@@ -97,6 +114,32 @@ def host_cores():
 
 def host_threads():
     return max(1, min(16, host_cores()))
+
+
+DUMP_LIMIT = 64 << 20  # bytes --dump-outputs may write in all
+
+
+def snapshot_outputs(tensors, seed=824):
+    """Host float32 copies of `tensors` (name -> tensor) for --dump-outputs,
+    taken at the call (later steps do not change them).  Every array gets an
+    equal share of DUMP_LIMIT; a larger one keeps a sorted row sample drawn
+    from RandomState(seed), the same rows for the same shape."""
+    share = DUMP_LIMIT // max(1, len(tensors))
+    out = {}
+    for name, t in tensors.items():
+        t = t.detach().reshape(1) if t.dim() == 0 else t.detach()
+        row_bytes = 4 * max(1, t[0].numel())
+        if t.shape[0] * row_bytes > share:
+            idx = np.sort(np.random.RandomState(seed).choice(t.shape[0], share // row_bytes, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        out[name] = np.ascontiguousarray(t.float().cpu().numpy())
+    return out
+
+
+def write_outputs(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name.replace(".", "_") + ".npy"), a)
 
 
 def build_workload(cfg, device, seed=824, world=1):
@@ -478,8 +521,13 @@ def run_apply_model_loop(args, cfg):
         ext += len(nodes)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        named = {"loss": torch.tensor([float(loss)])}
+        for prefix, m in (("graphsage", gsage), ("classification", cls)):
+            named.update({f"{prefix}.{k}": p for k, p in m.named_parameters()})
+        write_outputs(args.dump_outputs, snapshot_outputs(named, args.seed))
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline_loop(wl, cfg, batches, args.cpu_budget, args.seed)
     out = {
         "metric": "sampled nodes/sec (2-layer, fanout 25,10) at 1/2/4/8 MI355X",
@@ -559,8 +607,10 @@ def run_embed(args, cfg):
         emb.embed(warm, B, [train.make_rng(args.seed + 1, rank, w) for w in range(args.sampler_streams)])
     rngs = [train.make_rng(args.seed, rank, w) for w in range(args.sampler_streams)]
     n_units = -(-(len(mine) // B) // emb.merge)  # merged steps of emb.merge batches
-    n_timed = min(n_units, 200)  # event-bound launches cost host time: time the first 200 gathers
-    gs._lib.check(gs._lib.lib().gs_trainer_time_agg(emb.trainer._h, n_timed))
+    # --full: event-bound launches cost host time, so time the first 200 gathers only
+    n_timed = min(n_units, 200) if args.full else 0
+    if n_timed:
+        gs._lib.check(gs._lib.lib().gs_trainer_time_agg(emb.trainer._h, n_timed))
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -587,9 +637,17 @@ def run_embed(args, cfg):
         L = len(cfg["fanouts"])
         sizes = st["hop_sizes_sum"] / max(1, st["steps"])
         agg_bytes = agg1_ids_bytes(sizes[L - 1, 0], sizes[L - 1, 1], cfg["feat"], 4, cfg["fanouts"][-1])
-        achieved = float(agg_bytes) / (agg_ms * 1e-3) / 1e9
+        roof = None
+        if n_timed:
+            achieved = float(agg_bytes) / (agg_ms * 1e-3) / 1e9
+            roof = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
+                    "kernel": "agg_ids_kernel (layer-1 gather-mean over resolved neighbour ids)",
+                    "avg_launch_us": round(agg_ms * 1e3, 2), "algo_bytes_per_launch": int(agg_bytes)}
+        if args.dump_outputs:  # this rank's rows, in the order of its ids
+            write_outputs(args.dump_outputs, snapshot_outputs({"embeddings": E}, args.seed))
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cpu = cpu_baseline_embed(wl, cfg, args.cpu_budget, args.seed)
         out = {
             "metric": "embedded nodes/sec (get_gnn_embeddings, 2-layer, fanout 25,10)",
@@ -607,10 +665,7 @@ def run_embed(args, cfg):
                        "host_ms_per_batch": {k: round(1e3 * st[k + "_s"] / max(1, n_b), 4)
                                              for k in ("wait", "wait_sample", "wait_ring", "wait_gather", "issue")},
                        "lookahead_misses": st["lookahead_misses"]},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
-                         "kernel": "agg_ids_kernel (layer-1 gather-mean over resolved neighbour ids)",
-                         "avg_launch_us": round(agg_ms * 1e3, 2), "algo_bytes_per_launch": int(agg_bytes)},
+            "roofline": roof,
             "cpu_baseline": cpu,
         }
         print(json.dumps(out), flush=True)
@@ -650,7 +705,7 @@ def reference_stream_window(trainer, wl, cfg, args, batches):
             "lookahead_misses": st["lookahead_misses"]}
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
@@ -658,7 +713,13 @@ def main():
     ap.add_argument("--config", default="rmat2m", choices=sorted(CONFIGS))
     ap.add_argument("--batch", type=int, default=None)
     ap.add_argument("--seed", type=int, default=824)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: kernel timers and rooflines, the "
+                         "sustained and reference-stream windows, the sampled-node replay, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what their last step left (loss and parameters, or the "
+                         "embeddings) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=25.0)
     ap.add_argument("--full-graph", action="store_true", help="rmat2m-embed: embed every node id")
     ap.add_argument("--embed-merge", type=int, default=2,
@@ -686,7 +747,11 @@ def main():
     ap.add_argument("--sampler-helpers", type=int, default=None,
                     help="helper threads per sampler stream (same draws; lower per-batch latency); "
                          "default 0: more streams instead (profiles/r06_sampler_layout_ab.txt)")
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
     per_gpu = host_cores() // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1")))
     # as given on the command line, before the training runner's defaults below
     # (the pubmed loop and the inference runner pick their own)
@@ -735,9 +800,22 @@ def main():
     trainer = train.NativeTrainer(wl["graph"], wl["X"], wl["labels"], cfg["classes"], num_layers=2,
                                   hidden=128, fanouts=cfg["fanouts"], agg_func=cfg["agg"], seed=args.seed)
     rngs = [train.make_rng(args.seed, rank, w) for w in range(args.sampler_streams)]
-    calib = min(50, args.steps)  # untimed steps after the measured ones that time the other kernels
-    sustain = max(0, args.sustain)  # then a steady-state window (sampler threads running ahead)
-    total_steps = args.warmup + 2 * args.steps + calib + sustain  # warmup, cold and steady windows, calib, sustain
+    # --full: untimed steps after the measured ones that time the other kernels,
+    # then a steady-state window (sampler threads running ahead)
+    calib = min(50, args.steps)
+    sustain = max(0, args.sustain)
+    # their batches are in the list of a plain run too, which never runs them: the sampler
+    # threads need batches past the timed window to go on sampling inside it, as in any
+    # later step of a training run (the steady window's clock waits for them)
+    tail = calib + sustain
+    if not args.full:
+        calib = sustain = 0
+    # the cold window fills the sampler pipeline (streams x depth batches) before the steady
+    # one: as long as the timed window, but in a plain run no longer than FILL_STEPS, so
+    # that a long run spends its time in the timed steps
+    fill = args.steps if args.full else min(args.steps, FILL_STEPS)
+    fill_len = "the same length" if fill == args.steps else f"{fill} steps"
+    total_steps = args.warmup + fill + args.steps + tail  # warmup, cold and steady windows, calib, sustain
     batches = []
     epoch = 0
     while len(batches) < total_steps:
@@ -755,39 +833,44 @@ def main():
     L = len(cfg["fanouts"])
     lib = gs._lib.lib()
 
-    # warmup: every timer site armed; the site with the longest median launch
-    # is the dominant kernel, the one timed inside the measured steps
+    # warmup; with --full every timer site armed: the site with the longest
+    # median launch is the dominant kernel, the one timed inside the measured steps
     runner.release(args.warmup)
-    gs._lib.check(lib.gs_trainer_time_kernels(trainer._h, (1 << len(SITES)) - 1, args.warmup))
+    if args.full:
+        gs._lib.check(lib.gs_trainer_time_kernels(trainer._h, (1 << len(SITES)) - 1, args.warmup))
     runner.run(args.warmup)
     torch.cuda.synchronize()
-    warm = {site: kernel_times_ms(trainer, args.warmup, site) for site in SITES}
-    names = {site: lib.gs_trainer_kernel_name(trainer._h, site).decode() for site in SITES}
-    # dominant: the timed site with the largest average duration in the committed
-    # rocprofv3 summary of this config (a stable choice: fwd, dW and top launches
-    # lie within ~1 us of each other under events), else the longest warmup median
-    prof_avg = {site: load_rocprof_avg(args.config, cfg["batch"], names[site]) for site in SITES}
-    if all(prof_avg[site] for site in SITES if len(warm[site])):
-        dominant = max((site for site in SITES if len(warm[site])), key=lambda site: prof_avg[site]["avg_us"])
-        dominant_by = f"largest average launch in the committed rocprofv3 summary ({prof_avg[dominant]['source']})"
-    else:
-        dominant = max(SITES, key=lambda site: float(np.median(warm[site])) if len(warm[site]) else -1.0)
-        dominant_by = "longest median launch (HIP events) over the warmup steps"
+    dominant = None
+    if args.full:
+        warm = {site: kernel_times_ms(trainer, args.warmup, site) for site in SITES}
+        names = {site: lib.gs_trainer_kernel_name(trainer._h, site).decode() for site in SITES}
+        # dominant: the timed site with the largest average duration in the committed
+        # rocprofv3 summary of this config (a stable choice: fwd, dW and top launches
+        # lie within ~1 us of each other under events), else the longest warmup median
+        prof_avg = {site: load_rocprof_avg(args.config, cfg["batch"], names[site]) for site in SITES}
+        if all(prof_avg[site] for site in SITES if len(warm[site])):
+            dominant = max((site for site in SITES if len(warm[site])), key=lambda site: prof_avg[site]["avg_us"])
+            dominant_by = f"largest average launch in the committed rocprofv3 summary ({prof_avg[dominant]['source']})"
+        else:
+            dominant = max(SITES, key=lambda site: float(np.median(warm[site])) if len(warm[site]) else -1.0)
+            dominant_by = "longest median launch (HIP events) over the warmup steps"
     if world > 1:
         dist.barrier()
     runner.stats(reset=True)
-    no_timer = bool(os.environ.get("GS_BENCH_NO_TIMER"))  # A/B of the in-window timer's cost
+    # a plain run times no kernel; GS_BENCH_NO_TIMER: A/B of the in-window timer's cost under --full
+    no_timer = not args.full or bool(os.environ.get("GS_BENCH_NO_TIMER"))
     # an event-bound launch idles the queue a few us on either side of it
     # (rocprofv3 trace: 4.4 us each side): time one launch in `every` of the
     # measured steps, spread over both windows, not all of them (one in 4 cost
     # the 20-step line 2.4 % against no timer: 7.74 against 7.93 M, medians of
     # six rounds; one in 8 leaves 6 timed launches over the two 20-step windows)
     every = max(8, args.steps // 16)
-    gs._lib.check(lib.gs_trainer_time_kernels_every(trainer._h, 0 if no_timer else 1 << dominant, 2 * args.steps,
-                                                    every))
+    if args.full:
+        gs._lib.check(lib.gs_trainer_time_kernels_every(trainer._h, 0 if no_timer else 1 << dominant,
+                                                        2 * args.steps, every))
 
-    def timed_window(wait_sampled):
-        """K steps between barrier + synchronize on both sides; with
+    def timed_window(n_steps, wait_sampled):
+        """n_steps steps between barrier + synchronize on both sides; with
         wait_sampled the clock also runs until the sampler threads have
         finished as many new batches as the window consumed."""
         if world > 1:
@@ -797,9 +880,9 @@ def main():
         ta = time.perf_counter()
         if not wait_sampled:  # cold: the sampler threads start the window's batches now
             runner.release(total_steps)
-        runner.run(args.steps)
+        runner.run(n_steps)
         if wait_sampled:
-            want = min(s0 + args.steps, total_steps)
+            want = min(s0 + n_steps, total_steps)
             deadline = time.perf_counter() + 60.0
             # spin (no sleep: a 50 us sleep overshot the condition by up to ~0.1 ms of a
             # ~1.3 ms window); the sampler threads are native and need no GIL
@@ -823,29 +906,33 @@ def main():
     thr0 = cgroup_throttle()
     # cold window: nothing past the warmup batches sampled before t0, so the
     # window pays the pipeline fill (the first batch's whole sampling latency)
-    cold_elapsed, cold_proof = timed_window(wait_sampled=False)
+    cold_elapsed, cold_proof = timed_window(fill, wait_sampled=False)
     cst = runner.stats(reset=True)  # the cold window's host stats; the line's own are the steady window's
     cold_proof.update(lookahead_misses=cst["lookahead_misses"], max_step_ms=round(1e3 * cst["max_step_s"], 3))
     # steady window (`value`): straight after it, the pipeline running as in
     # any later step of a training run; the clock stops only once the window
     # has also sampled as many new batches as it consumed, so the sampling
     # work of every step it counts is inside the timed region
-    elapsed, proof = timed_window(wait_sampled=True)
+    elapsed, proof = timed_window(args.steps, wait_sampled=True)
     thr1 = cgroup_throttle()
     st = runner.stats()
+    dump = None
+    if args.dump_outputs and rank == 0:  # the state the last timed step left (ranks hold equal parameters)
+        dump = snapshot_outputs({"loss": trainer.loss, **trainer.p.state_dict()}, args.seed)
     times = {} if no_timer else {dominant: kernel_times_ms(trainer, 2 * args.steps // every, dominant)}
     blocks = {} if no_timer else {dominant: block_stats_us(trainer, 2 * args.steps // every, dominant)}
-    # calibration steps after the measured ones time the other sites (an
-    # event-bound launch costs the stream a little: never inside the timed steps)
-    runner.release(total_steps)
-    others = sum(1 << site for site in SITES if site != dominant or no_timer)
-    gs._lib.check(lib.gs_trainer_time_kernels(trainer._h, others, calib))
-    runner.run(calib)
-    torch.cuda.synchronize()
-    for site in SITES:
-        if site not in times:
-            times[site] = kernel_times_ms(trainer, calib, site)
-            blocks[site] = block_stats_us(trainer, calib, site)
+    if args.full:
+        # calibration steps after the measured ones time the other sites (an
+        # event-bound launch costs the stream a little: never inside the timed steps)
+        runner.release(total_steps)
+        others = sum(1 << site for site in SITES if site != dominant or no_timer)
+        gs._lib.check(lib.gs_trainer_time_kernels(trainer._h, others, calib))
+        runner.run(calib)
+        torch.cuda.synchronize()
+        for site in SITES:
+            if site not in times:
+                times[site] = kernel_times_ms(trainer, calib, site)
+                blocks[site] = block_stats_us(trainer, calib, site)
     loss = float(trainer.loss.item())
     # steady state: the remaining batches, with the sampler threads free to run
     # ahead (released since the calibration steps); reported beside `value`
@@ -881,7 +968,7 @@ def main():
     value = cfg["batch"] * args.steps * world / elapsed
     sizes = st["hop_sizes_sum"] / max(1, st["steps"])  # mean (n_dst, n_pos, n_src, n_nbr) per hop
     ref_stream = None
-    if world == 1 and args.ref_stream_steps > 0 and args.sampler == "host":
+    if args.full and world == 1 and args.ref_stream_steps > 0 and args.sampler == "host":
         runner.close()  # its sampler threads are done (the batch list is consumed)
         runner = None
         ref_stream = reference_stream_window(trainer, wl, cfg, args, batches)
@@ -893,13 +980,16 @@ def main():
 
     # the BASELINE metric literally: sampled nodes (B + |L1| + |L0|, the
     # reference's nodes_batch_layers) per second over the steady window's batches
-    w0 = args.warmup + args.steps  # the steady window's first batch
-    fr = replay_frontiers(wl["graph"], batches, args.sampler_streams, cfg["fanouts"], args.seed, rank,
-                          w0 + args.steps)[w0:]
-    nodes_t = torch.tensor([float(fr.sum())], dtype=torch.float64, device=device)
-    if world > 1:
-        dist.all_reduce(nodes_t)
-    sampled_nodes_per_s = float(nodes_t.item()) / elapsed
+    # (--full: a host replay of every batch up to the window's last)
+    fr = sampled_nodes_per_s = None
+    if args.full:
+        w0 = args.warmup + args.steps  # the steady window's first batch
+        fr = replay_frontiers(wl["graph"], batches, args.sampler_streams, cfg["fanouts"], args.seed, rank,
+                              w0 + args.steps)[w0:]
+        nodes_t = torch.tensor([float(fr.sum())], dtype=torch.float64, device=device)
+        if world > 1:
+            dist.all_reduce(nodes_t)
+        sampled_nodes_per_s = float(nodes_t.item()) / elapsed
     # sampler capacity: S streams, each a batch per mean sampling time
     per_batch_s = st["sample_s"] / max(1, st["steps"])
     cap_batches = args.sampler_streams / per_batch_s if per_batch_s > 0 else float("inf")
@@ -961,16 +1051,18 @@ def main():
                 timed_in=(f"{len(tt)} of the measured steps of both windows (one in {every})" if site == dominant else f"{calib} calibration steps after them"),
                 warmup_median_us=round(float(np.median(warm[site])) * 1e3, 2) if len(warm[site]) else None,
                 workgroup_us=blocks.get(site), **work)
-        roof = dict(rooflines[SITE_NAMES[dominant]])
-        roof["dominant_by"] = dominant_by
+        roof = None
+        if args.full:
+            roof = dict(rooflines[SITE_NAMES[dominant]])
+            roof["dominant_by"] = dominant_by
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cpu = cpu_baseline(wl, cfg, args.cpu_budget, args.seed)
         out = {
             "metric": "sampled nodes/sec (2-layer, fanout 25,10) at 1/2/4/8 MI355X",
             "value": round(value, 1), "unit": "root nodes/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "sampled_nodes_per_s": round(sampled_nodes_per_s, 1),
+            "sampled_nodes_per_s": round(sampled_nodes_per_s, 1) if args.full else None,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": cfg["dtype"],
             "data": "synthetic (R-MAT graph, hashed U(-1,1) features, labels id%16)",
             "config": {"workload": f"{args.config}: R-MAT scale {cfg['scale']} "
@@ -984,18 +1076,18 @@ def main():
                        "sampler_contexts_warmed": not args.no_warm,
                        "sampled_nodes": {"per_step_mean": [round(float(x), 1) for x in fr.mean(0)],
                                          "fields": "B, |L1|, |L0| (unique frontiers, models.py:246-251)",
-                                         "per_s": round(sampled_nodes_per_s, 1)},
+                                         "per_s": round(sampled_nodes_per_s, 1)} if args.full else None,
                        "sampler": {"host_cores_per_gpu": args.per_gpu, "layout_cores": args.layout_cores,
                                    "ms_per_batch": round(per_batch_s * 1e3, 4),
                                    "capacity_batches_per_s": round(cap_batches, 1),
                                    "capacity_roots_per_s": round(cap_batches * cfg["batch"], 1),
                                    "produced_batches_per_s_in_window": round(produced, 1),
                                    "sampler_bound": bool(sampler_bound)},
-                       "window": "steady (after a cold window of the same length; the clock waits until the "
-                                 "window has sampled as many new batches as it consumed)",
+                       "window": f"steady (after a cold window of {fill_len}; "
+                                 "the clock waits until the window has sampled as many new batches as it consumed)",
                        **proof,
-                       "cold_start": {"value": round(cfg["batch"] * args.steps * world / cold_elapsed, 1),
-                                      "ms_per_step": round(cold_elapsed / args.steps * 1e3, 4), **cold_proof},
+                       "cold_start": {"value": round(cfg["batch"] * fill * world / cold_elapsed, 1), "steps": fill,
+                                      "ms_per_step": round(cold_elapsed / fill * 1e3, 4), **cold_proof},
                        "allreduce_buckets": args.ar_buckets if world > 1 else 0,
                        "allreduce_w1_chunks": (int(os.environ.get("GS_AR_W1_CHUNKS", "2"))
                                                if world > 1 and args.ar_buckets == 2 else 0),
@@ -1015,11 +1107,13 @@ def main():
                                             "max_step": round(1e3 * st["max_step_s"], 3)},
                        "cgroup_throttled_ms": (round((thr1 - thr0) / 1e3, 3) if thr0 is not None else None)},
             "roofline": roof,
-            "roofline_kernels": rooflines,
+            "roofline_kernels": rooflines if args.full else None,
             "sustained": sus,
             "reference_stream": ref_stream,
             "cpu_baseline": cpu,
         }
+        if dump is not None:
+            write_outputs(args.dump_outputs, dump)
         print(json.dumps(out), flush=True)
     if runner is not None:
         runner.close()

@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 for i in $(seq 1 ${ROUNDS:-6}); do
   for l in "$@"; do
     s=${l%%:*}; h=${l##*:}
-    timeout -k 10 200 python bench.py --steps ${STEPS:-20} --warmup 5 --sustain 200 --no-cpu-baseline \
+    timeout -k 10 200 python bench.py --full --steps ${STEPS:-20} --warmup 5 --sustain 200 --no-cpu-baseline \
         --sampler-streams $s --sampler-helpers $h > gpurun_out/abl.log 2>&1 || exit 1
     python -c "import json;d=json.loads(open('gpurun_out/abl.log').read().splitlines()[-1]);print('$l', d['value'], d['sustained']['value'])" | tee -a gpurun_out/abl_n.txt
   done

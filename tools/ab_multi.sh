@@ -11,7 +11,7 @@ for i in $(seq 1 ${ROUNDS:-3}); do
   for so in "$@"; do
     src=$so; [ "$so" = "$P/libgraphsage_amd.so" ] && src=/tmp/lib_main.so
     cp $src $P/libgraphsage_amd.so
-    timeout -k 10 200 python bench.py --steps ${STEPS:-300} --warmup 10 --sustain ${SUSTAIN:-300} --no-cpu-baseline \
+    timeout -k 10 200 python bench.py --full --steps ${STEPS:-300} --warmup 10 --sustain ${SUSTAIN:-300} --no-cpu-baseline \
         --ref-stream-steps 0 > gpurun_out/ab.log 2>&1 || { cp /tmp/lib_main.so $P/libgraphsage_amd.so; exit 1; }
     python -c "import json;d=json.loads(open('gpurun_out/ab.log').read().splitlines()[-1]);print('$(basename $so)', d['ms_per_step'], d['sustained']['ms_per_step'], ' '.join(f'{k}={v[\"avg_launch_us\"]}' for k, v in d['roofline_kernels'].items()))" | tee -a gpurun_out/ab_multi.txt
   done

@@ -15,7 +15,7 @@ for i in $(seq 1 ${ROUNDS:-2}); do
     cp $src $P/libgraphsage_amd.so
     tag=$(basename $so .so)_$i
     timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/$tag -o run --output-format csv -- \
-        python3 bench.py --steps ${STEPS:-300} --warmup 10 --sustain ${SUSTAIN:-300} --no-cpu-baseline \
+        python3 bench.py --full --steps ${STEPS:-300} --warmup 10 --sustain ${SUSTAIN:-300} --no-cpu-baseline \
         --ref-stream-steps 0 ${BENCH_ARGS} > $OUT/$tag.log 2>&1 || { cp /tmp/lib_main.so $P/libgraphsage_amd.so; exit 1; }
     python3 tools/ab_prof_line.py $(basename $so) $OUT/$tag $OUT/$tag.log | tee -a $OUT/runs.txt
   done

@@ -19,6 +19,6 @@ run() {  # name, timeout, bench args...
   grep '^{"metric"' $O/bench_$n.log | tail -1 > $O/bench_$n.json; cut -c1-240 $O/bench_$n.json
 }
 case "${BENCH:-none}" in
-  default) run default 400 ;;
+  default) run default 400 --full ;;
   *) ;;
 esac

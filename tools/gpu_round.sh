@@ -15,7 +15,7 @@ if [ -z "$SKIP_TESTS" ]; then
   rc=$?; echo "smoke rc=$rc"; tail -2 "$OUT/smoke.log"; [ $rc -eq 0 ] || exit $rc
 fi
 for S in ${STREAMS:-1 4}; do
-  timeout -k 10 600 python bench.py --steps ${STEPS:-100} --warmup 10 --sampler-streams $S ${BENCH_ARGS} \
+  timeout -k 10 600 python bench.py --full --steps ${STEPS:-100} --warmup 10 --sampler-streams $S ${BENCH_ARGS} \
       > "$OUT/bench_s$S.log" 2>&1
   rc=$?; echo "bench streams=$S rc=$rc"; tail -1 "$OUT/bench_s$S.log"; [ $rc -eq 0 ] || exit $rc
   BENCH_ARGS="$BENCH_ARGS --no-cpu-baseline"
@@ -23,7 +23,7 @@ done
 if [ -n "$PROF" ]; then
   mkdir -p "$OUT/prof_$PROF"
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_$PROF" -o run --output-format csv -- \
-      python3 bench.py --steps 50 --warmup 10 --no-cpu-baseline --sampler-streams ${PROF_STREAMS:-4} ${PROF_ARGS} \
+      python3 bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --sampler-streams ${PROF_STREAMS:-4} ${PROF_ARGS} \
       > "$OUT/prof_$PROF/bench.log" 2>&1
   rc=$?; echo "rocprof rc=$rc"; tail -1 "$OUT/prof_$PROF/bench.log"; exit $rc
 fi

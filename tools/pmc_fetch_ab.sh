@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 for e in "$@"; do
   D=gpurun_out/pmcab_${e//[=\/]/_}; mkdir -p $D
   env $e timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d $D -o run --output-format csv -- \
-      python3 bench.py --steps 30 --warmup 5 --sustain 0 --no-cpu-baseline > $D/bench.log 2>&1 || exit $?
+      python3 bench.py --full --steps 30 --warmup 5 --sustain 0 --no-cpu-baseline > $D/bench.log 2>&1 || exit $?
   python3 - "$D" "$e" <<'PY'
 import csv, glob, sys, collections
 rows = []

@@ -10,5 +10,5 @@ mkdir -p "$OUT"
 cd "$ROOT"
 timeout -k 10 600 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAVES GRBM_GUI_ACTIVE \
     -d "$OUT/pmc" -o run --output-format csv -- \
-    python3 bench.py --steps 30 --warmup 5 --sustain 0 --no-cpu-baseline ${BENCH_ARGS} > "$OUT/bench.log" 2>&1 || exit $?
+    python3 bench.py --full --steps 30 --warmup 5 --sustain 0 --no-cpu-baseline ${BENCH_ARGS} > "$OUT/bench.log" 2>&1 || exit $?
 python3 tools/pmc_mfma_summary.py "$OUT" > "$OUT/summary.json" && cat "$OUT/summary.json"

@@ -10,6 +10,6 @@ mkdir -p "$OUT"
 cd "$ROOT"
 for C in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 600 rocprofv3 --pmc $C -d "$OUT/$C" -o run --output-format csv -- \
-      python3 bench.py --steps 30 --warmup 5 --no-cpu-baseline ${BENCH_ARGS} > "$OUT/bench_$C.log" 2>&1 || exit $?
+      python3 bench.py --full --steps 30 --warmup 5 --no-cpu-baseline ${BENCH_ARGS} > "$OUT/bench_$C.log" 2>&1 || exit $?
 done
 python3 tools/pmc_summary.py "$OUT" "${CONFIG:-rmat2m}" > "$OUT/summary.json" && cat "$OUT/summary.json"
