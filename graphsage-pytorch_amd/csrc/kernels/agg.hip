@@ -300,7 +300,7 @@ static int agg_ids_block_cap() { return 1 << 30; }
 
 void agg_ids_launch(gs_agg op, gs_dtype dt, const void* X, int64_t ldx, int64_t F, int64_t n_dst, int k,
                     const int32_t* ids, const int32_t* dst_ids, int gcn, void* out, int64_t ldo, hipStream_t st,
-                    void* self_out, int64_t ldso) {
+                    void* self_out, int64_t ldso, LaunchTimer* timer) {
     GS_REQUIRE(op == GS_AGG_MEAN || op == GS_AGG_MAX, GS_EINVAL, "agg_func must be MEAN or MAX");
     GS_REQUIRE(F >= 1 && n_dst >= 0 && k >= 1 && ldx >= F && ldo >= F, GS_EINVAL, "bad sizes");
     GS_REQUIRE(!self_out || (dst_ids && ldso >= F), GS_EINVAL, "self rows need dst_ids and ldso >= F");
@@ -314,11 +314,11 @@ void agg_ids_launch(gs_agg op, gs_dtype dt, const void* X, int64_t ldx, int64_t 
     do {                                                                                                         \
         const dim3 grid_(std::min((n + (kBlock / GG) - 1) / (kBlock / GG), cap));                                \
         if (self_out)                                                                                            \
-            launch_k(agg_ids_kernel<OPV, TT, VV, GG, true, ONE, NRV>, grid_, dim3(kBlock), 0, st,                \
+            launch_k(timer, agg_ids_kernel<OPV, TT, VV, GG, true, ONE, NRV>, grid_, dim3(kBlock), 0, st,         \
                      static_cast<const TT*>(X), ldx, f, n, k, ids, dst_ids, gcn, static_cast<TT*>(out), ldo,      \
                      static_cast<TT*>(self_out), ldso);                                                          \
         else                                                                                                     \
-            launch_k(agg_ids_kernel<OPV, TT, VV, GG, false, ONE, NRV>, grid_, dim3(kBlock), 0, st,               \
+            launch_k(timer, agg_ids_kernel<OPV, TT, VV, GG, false, ONE, NRV>, grid_, dim3(kBlock), 0, st,        \
                      static_cast<const TT*>(X), ldx, f, n, k, ids, dst_ids, gcn, static_cast<TT*>(out), ldo,      \
                      static_cast<TT*>(nullptr), ldso);                                                           \
     } while (0)
@@ -368,19 +368,19 @@ void agg_ids_launch(gs_agg op, gs_dtype dt, const void* X, int64_t ldx, int64_t 
 template <int OP, typename T, bool EXPAND>
 static void launch_fwd(int vec, const T* X, int64_t ldx, int F, int n_dst, const int* ptr,
                        const int* idx, const int64_t* row_ptr, const int* col, const int* dst_ids,
-                       int gcn, T* out, int64_t ldo, int* am, hipStream_t st) {
+                       int gcn, T* out, int64_t ldo, int* am, hipStream_t st, LaunchTimer* timer) {
     constexpr int V = sizeof(T) == 4 ? 4 : 8;
     if (vec == 1) {
         const dim3 grid((n_dst + (kBlock / 64) - 1) / (kBlock / 64));
-        launch_k(agg_fwd_kernel<OP, T, 1, 64, EXPAND>, grid, dim3(kBlock), 0, st, X, ldx, F, n_dst, ptr, idx, row_ptr,
-                 col, dst_ids, gcn, out, ldo, am);
+        launch_k(timer, agg_fwd_kernel<OP, T, 1, 64, EXPAND>, grid, dim3(kBlock), 0, st, X, ldx, F, n_dst, ptr, idx,
+                 row_ptr, col, dst_ids, gcn, out, ldo, am);
         return;
     }
     const int G = pick_group(F, V);
     const dim3 grid((n_dst + (kBlock / G) - 1) / (kBlock / G));
 #define GS_AGG_FWD(GG)                                                                                   \
-    launch_k(agg_fwd_kernel<OP, T, V, GG, EXPAND>, grid, dim3(kBlock), 0, st, X, ldx, F, n_dst, ptr, idx, row_ptr, \
-             col, dst_ids, gcn, out, ldo, am)
+    launch_k(timer, agg_fwd_kernel<OP, T, V, GG, EXPAND>, grid, dim3(kBlock), 0, st, X, ldx, F, n_dst, ptr, idx, \
+             row_ptr, col, dst_ids, gcn, out, ldo, am)
     if (G == 16) GS_AGG_FWD(16);
     else if (G == 32) GS_AGG_FWD(32);
     else GS_AGG_FWD(64);
@@ -408,37 +408,30 @@ static void launch_bwd(int vec, int n_src, int F, const int* tptr, const int* ti
 #undef GS_AGG_BWD
 }
 
-}  // namespace gs
-
-extern "C" {
-
-int gs_agg_fwd(gs_agg op, gs_dtype xdt, const void* X, int64_t ldx, int64_t F, int64_t n_dst,
-               const int32_t* ptr, const int32_t* idx, const int64_t* row_ptr, const int32_t* col,
-               const int32_t* dst_ids, int32_t gcn, void* out, gs_dtype odt, int64_t ldo,
-               int32_t* argmax, void* stream) {
-    GS_API_BEGIN
-    using namespace gs;
+void agg_fwd_launch(gs_agg op, gs_dtype xdt, const void* X, int64_t ldx, int64_t F, int64_t n_dst,
+                    const int32_t* ptr, const int32_t* idx, const int64_t* row_ptr, const int32_t* col,
+                    const int32_t* dst_ids, int32_t gcn, void* out, gs_dtype odt, int64_t ldo, int32_t* argmax,
+                    hipStream_t st, LaunchTimer* timer) {
     GS_REQUIRE(op == GS_AGG_MEAN || op == GS_AGG_MAX, GS_EINVAL, "agg_func must be MEAN or MAX");
     GS_REQUIRE(xdt == odt, GS_EINVAL, "output dtype must equal feature dtype");
     GS_REQUIRE(F >= 1 && F < (1 << 30) && n_dst >= 0 && n_dst < (int64_t(1) << 31), GS_EINVAL, "bad sizes");
     GS_REQUIRE(ldx >= F && ldo >= F, GS_EINVAL, "leading dimension smaller than F");
-    if (n_dst == 0) return GS_OK;
+    if (n_dst == 0) return;
     GS_REQUIRE(X && ptr && idx && out, GS_EINVAL, "NULL device pointer");
     const bool expand = col != nullptr;
     GS_REQUIRE(!expand || dst_ids, GS_EINVAL, "expand mode needs dst_ids");
     GS_REQUIRE(!(argmax && expand), GS_EINVAL, "argmax is only produced in explicit mode");
     const int V = xdt == GS_F32 ? 4 : 8;
     const int vec = (F % V == 0 && ldx % V == 0 && ldo % V == 0 && aligned16(X) && aligned16(out)) ? V : 1;
-    hipStream_t st = as_stream(stream);
     const int f = static_cast<int>(F), n = static_cast<int>(n_dst);
 #define GS_DISPATCH(OPV, TT)                                                                              \
     do {                                                                                                  \
         if (expand)                                                                                       \
             launch_fwd<OPV, TT, true>(vec, static_cast<const TT*>(X), ldx, f, n, ptr, idx, row_ptr, col,  \
-                                      dst_ids, gcn, static_cast<TT*>(out), ldo, nullptr, st);             \
+                                      dst_ids, gcn, static_cast<TT*>(out), ldo, nullptr, st, timer);      \
         else                                                                                              \
             launch_fwd<OPV, TT, false>(vec, static_cast<const TT*>(X), ldx, f, n, ptr, idx, nullptr,      \
-                                       nullptr, nullptr, 0, static_cast<TT*>(out), ldo, argmax, st);      \
+                                       nullptr, nullptr, 0, static_cast<TT*>(out), ldo, argmax, st, timer); \
     } while (0)
     if (op == GS_AGG_MEAN) {
         if (xdt == GS_F32) GS_DISPATCH(GS_AGG_MEAN, float);
@@ -449,6 +442,19 @@ int gs_agg_fwd(gs_agg op, gs_dtype xdt, const void* X, int64_t ldx, int64_t F, i
     }
 #undef GS_DISPATCH
     check_launch("gs_agg_fwd");
+}
+
+}  // namespace gs
+
+extern "C" {
+
+int gs_agg_fwd(gs_agg op, gs_dtype xdt, const void* X, int64_t ldx, int64_t F, int64_t n_dst,
+               const int32_t* ptr, const int32_t* idx, const int64_t* row_ptr, const int32_t* col,
+               const int32_t* dst_ids, int32_t gcn, void* out, gs_dtype odt, int64_t ldo,
+               int32_t* argmax, void* stream) {
+    GS_API_BEGIN
+    gs::agg_fwd_launch(op, xdt, X, ldx, F, n_dst, ptr, idx, row_ptr, col, dst_ids, gcn, out, odt, ldo, argmax,
+                       gs::as_stream(stream));
     GS_API_END
 }
 

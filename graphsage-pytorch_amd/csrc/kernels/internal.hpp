@@ -33,16 +33,27 @@ void trainer_keep_lowp(gs_trainer* t, bool keep);
 // those of the separate update launch.
 bool trainer_defer_update(gs_trainer* t, bool on, hipStream_t st, bool comm = false);
 int64_t trainer_w1_floats(const gs_trainer* t);
+// The runner's step-completion flag (DoneFlag, kcommon.hpp) for the step about
+// to be issued: the trainer hands it to the one launch of the step that
+// stores it (the slab-sum pair that writes the deferred update, else the
+// step's SGD / norm launch) and forgets it.  ptr == nullptr: none.
+void trainer_set_done(gs_trainer* t, int64_t* ptr, int64_t value);
+bool trainer_done_taken(const gs_trainer* t);  // a launch took the flag (or none was set)
 
 // linear.hip
-// Whether gs_sage_linear_fwd takes the wide (16-B load) kernel for these
-// operands: the only forward that applies a pending deferred update.
+// Whether the forward takes the wide (16-B load) kernel for these operands:
+// the only forward that applies a pending deferred update.
 bool linear_fwd_wide_ok(gs_dtype dt, int64_t F, const void* Xs, int64_t ldxs, const void* A, int64_t lda,
                         const void* W);
+// gs_sage_linear_fwd; pend: a pending clip + SGD this launch applies (the
+// wide kernel only; nullptr or !pend->on: none), timer: a timed launch.
+void linear_fwd_launch(gs_dtype dt, int64_t n, int64_t F, int64_t H, const void* Xs, int64_t ldxs,
+                       const int32_t* sidx, const void* A, int64_t lda, const void* Wd, float* out, int64_t ldo,
+                       int32_t relu, hipStream_t st, const FwdSpec* pend = nullptr, LaunchTimer* timer = nullptr);
 int linear_dw_slabs(gs_dtype dt, int64_t n, int64_t F, int64_t H, const void* Xs, int64_t ldxs,
                     const int32_t* sidx, const void* A, int64_t lda, const float* dout, const float* out,
                     int64_t ldo, int32_t relu, float* dW, void* ws, int64_t ws_bytes, hipStream_t st,
-                    int64_t H_split = -1, int phases = 1);
+                    int64_t H_split = -1, int phases = 1, LaunchTimer* timer = nullptr);
 // Row phases of the layer-1 weight gradient (linear_dw_body<PH>): 512-thread
 // workgroups, half the slabs.  Layers >= 2 keep one phase (the fused layer
 // backward's slabs, which the unfused path must match).
@@ -62,9 +73,10 @@ struct SlabSum {
 bool sum_slabs_pair_ok(int64_t len1, int64_t len2);
 int sum_slabs_pair_parts2(int64_t len2);
 // spec_S: also W1's speculative update spec_S = spec_P - lr·(layer-1 sum) (the
-// trainer's deferred update), and the launch takes the done flag (g_done_flag).
+// trainer's deferred update), and the launch stores the done flag.
 int sum_slabs_pair_launch(const SlabSum& s1, const SlabSum& s2, hipStream_t st, const float* spec_P = nullptr,
-                          float* spec_S = nullptr, float lr = 0.f, uint16_t* spec_S_lp = nullptr);
+                          float* spec_S = nullptr, float lr = 0.f, uint16_t* spec_S_lp = nullptr, DoneFlag done = {},
+                          LaunchTimer* timer = nullptr);
 // The pending update's tail at the end of a deferred-update run: the flat
 // parameters and gradients become what the separate clip + SGD launch would
 // have left (W1 from sp.S or recomputed into w1_out, the others updated).
@@ -88,20 +100,31 @@ void trainer_reserve_top(gs_trainer* t, int64_t B, int32_t tk);
 // self_out (optional): each destination's own row X[dst_ids[r]] copied to self_out[r]
 void agg_ids_launch(gs_agg op, gs_dtype dt, const void* X, int64_t ldx, int64_t F, int64_t n_dst, int k,
                     const int32_t* ids, const int32_t* dst_ids, int gcn, void* out, int64_t ldo, hipStream_t st,
-                    void* self_out = nullptr, int64_t ldso = 0);
+                    void* self_out = nullptr, int64_t ldso = 0, LaunchTimer* timer = nullptr);
+// gs_agg_fwd (its argument checks included)
+void agg_fwd_launch(gs_agg op, gs_dtype xdt, const void* X, int64_t ldx, int64_t F, int64_t n_dst,
+                    const int32_t* ptr, const int32_t* idx, const int64_t* row_ptr, const int32_t* col,
+                    const int32_t* dst_ids, int32_t gcn, void* out, gs_dtype odt, int64_t ldo, int32_t* argmax,
+                    hipStream_t st, LaunchTimer* timer = nullptr);
 
 // misc.hip
 int cls_rows_launch(int64_t B, int64_t D, int64_t C, const float* E, const float* Wc, const float* bc,
                     const int32_t* labels, const int32_t* roots, int32_t mask_relu, float* dE, float* ws,
                     hipStream_t st);
+// The clip + SGD launches: shadow, a bf16 copy of a parameter range written
+// beside the update; done, the step-completion flag the SGD launch stores.
 void sgd_with_parts(int32_t n_groups, const int64_t* goff_host, const int* npart, int pstride, float* params,
-                    float* grads, const float* part, float grad_scale, float max_norm, float lr, hipStream_t st);
+                    float* grads, const float* part, float grad_scale, float max_norm, float lr, hipStream_t st,
+                    LowpShadow shadow = {}, DoneFlag done = {});
+// gs_clip_sgd (the norm launch, then the SGD)
+void clip_sgd_launch(int32_t n_groups, const int64_t* goff_host, float* params, float* grads, float grad_scale,
+                     float max_norm, float lr, float* ws, hipStream_t st, LowpShadow shadow = {}, DoneFlag done = {});
 // The deferred update after an all-reduce: gs_clip_sgd's norm partials (into
 // part, kNormBlocks per group; returns that count) and W1's speculative update
-// S = P - lr·(scale·g) (+ S_lp in bf16) for the elements [0, n1); takes the
+// S = P - lr·(scale·g) (+ S_lp in bf16) for the elements [0, n1); stores the
 // done flag.
 int sumsq_spec_launch(int32_t n_groups, const int64_t* goff_host, const float* grads, float* part, const float* P,
-                      float* S, uint16_t* S_lp, int64_t n1, float lr, float scale, hipStream_t st);
+                      float* S, uint16_t* S_lp, int64_t n1, float lr, float scale, hipStream_t st, DoneFlag done = {});
 
 // bwd.hip: the backward of one layer l >= 2 (fp32 activations, relu already
 // folded into dZ) in two launches, each running independent kernels side by
@@ -190,7 +213,7 @@ bool top_supported(int64_t H, int64_t C, bool gcn);
 int top_fwd_bwd(int agg, int64_t B, int64_t C, const float* Hprev, const int32_t* ptr, const int32_t* nbr,
                 const int32_t* self, const float* W, const float* Wc, const float* bc, const int32_t* labels,
                 const int32_t* roots, float* aggo, int32_t* argmax, float* E, float* dZ, float* dIn, float* slab,
-                hipStream_t st, const int32_t* tids = nullptr, int tk = 0);
+                hipStream_t st, const int32_t* tids = nullptr, int tk = 0, LaunchTimer* timer = nullptr);
 // The pair form (C <= 16): two blocks per 4 roots, each with half of W2 and
 // E's columns, the partial logits exchanged between the pair as tagged
 // granules (xch: [8·ceil(quads / 8)][2][64] u64, zero at allocation; epoch:
@@ -203,7 +226,7 @@ int top_pair_fwd_bwd(int agg, int64_t B, int64_t C, const float* Hprev, const in
                      const int32_t* self, const float* W, const float* Wc, const float* bc, const int32_t* labels,
                      const int32_t* roots, float* aggo, int32_t* argmax, float* E, float* dZ, float* dIn, float* dIn2,
                      float* slab, unsigned long long* xch, unsigned epoch, unsigned* fail, hipStream_t st,
-                     const int32_t* tids = nullptr, int tk = 0);
+                     const int32_t* tids = nullptr, int tk = 0, LaunchTimer* timer = nullptr);
 inline int64_t top_pair_xch_words(int64_t B) { return 8 * ((((B + 3) / 4) + 7) / 8) * 2 * 64; }
 
 // dsample.hip: whether the last gs_dsampler_run has completed (no wait).

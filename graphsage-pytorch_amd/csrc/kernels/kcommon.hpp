@@ -162,64 +162,68 @@ inline void check_launch(const char* what) {
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
-// Kernel-bound timing: when armed (by the trainer's roofline timer), the next
-// launch through launch_k binds the two events to its own dispatch packet
-// (hipExtLaunchKernel), so their elapsed time is the kernel's begin-to-end
-// span, the quantity rocprofv3's kernel trace reports, without the marker
-// packets' dispatch overhead.  Cleared by that launch.
-struct LaunchEvents {
-    hipEvent_t start = nullptr, stop = nullptr;
-};
-inline thread_local LaunchEvents g_launch_events;
-// The (mangled) symbol of the last kernel launch_k bound to timing events, so
-// a timer site reports which kernel variant it actually timed.
-inline thread_local const char* g_launch_name = nullptr;
-
-// In-kernel span of a timed launch (the bench's roofline timers, step.hip):
-// when set, the next launch of a kernel that supports it (the layer-1 wide
-// forward, the top launch) stores the 100 MHz s_memrealtime clock at each
+// In-kernel span of a timed launch (the bench's roofline timers, step.hip): a
+// kernel that supports it (the layer-1 wide forward, the dW GEMM, the top
+// launch, the slab-sum pair) stores the 100 MHz s_memrealtime clock at each
 // workgroup's start and end (plain stores, one slot per workgroup: no
 // atomics on a shared word, which serialise across the chip), and the host
 // takes min(start) .. max(end): the first-wave-to-last-wave span rocprofv3's
-// kernel trace reports.  The launcher takes it (and drops g_launch_events: an
-// event pair's start marker is processed before the dispatch, so its span
-// also covers the wait for the previous launch of a full queue).
+// kernel trace reports.
 constexpr int kStampBlocks = 1024;  // workgroups per timed launch with a slot (more: not timed)
 struct KStamp {
     unsigned long long* start = nullptr;  // [kStampBlocks], zeroed
     unsigned long long* end = nullptr;
 };
-inline thread_local KStamp g_kernel_stamp;
 
-// Host-visible step-completion flag (runtime/runner.hip): when set, the next
-// SGD launch of this thread stores `value` into `ptr` (fine-grained pinned
-// memory, system scope) from its first thread at kernel start -- by stream
-// order every earlier launch of the step has completed then -- and clears it.
-// This replaces an event record between steps (a marker packet that idled
-// the queue ~4.4 us, rocprofv3 trace).
+// One timed launch (the trainer's roofline timer passes it down to the
+// launcher of the kernel it times; no timer, or one without events, means
+// "not timed").  A launcher whose kernel stores its own span hands it
+// take_stamp(); otherwise launch_k binds the two events to the kernel's own
+// dispatch packet (hipExtLaunchKernel), so their elapsed time is the kernel's
+// begin-to-end span, without the marker packets' dispatch overhead.  A
+// stamped kernel drops the events: an event pair's start marker is processed
+// before the dispatch, so its span also covers the wait for the previous
+// launch of a full queue.
+struct LaunchTimer {
+    hipEvent_t start = nullptr, stop = nullptr;  // bound to the dispatch when the kernel does not stamp
+    KStamp stamp;                  // slots for a kernel that stores its own span (may be empty)
+    const char* kernel = nullptr;  // out: the (mangled) symbol of the kernel launched
+    bool stamped = false;          // out: the kernel took the stamp
+    KStamp take_stamp() {
+        stamped = stamp.start != nullptr;
+        return stamp;
+    }
+};
+inline KStamp take_stamp(LaunchTimer* tm) { return tm ? tm->take_stamp() : KStamp{}; }
+
+// Host-visible step-completion flag (runtime/runner.hip): the launch it is
+// handed to (the step's SGD launch, or the launch that writes the deferred
+// update) stores `value` into `ptr` (fine-grained pinned memory, system scope)
+// from its first thread at kernel start -- by stream order every earlier
+// launch of the step has completed then.  This replaces an event record
+// between steps (a marker packet that idled the queue ~4.4 us, rocprofv3
+// trace).  Empty: no flag.
 struct DoneFlag {
     int64_t* ptr = nullptr;
     int64_t value = 0;
 };
-inline thread_local DoneFlag g_done_flag;
 
-// bf16 copy of a parameter range the next SGD launch of this thread writes
-// beside the fp32 update (gs_trainer's W1 shadow for bf16 features: the next
-// forward reads it instead of casting W1 again), then clears.
+// bf16 copy of a parameter range that an SGD launch writes beside the fp32
+// update (gs_trainer's W1 shadow for bf16 features: the next forward reads it
+// instead of casting W1 again).  Empty: no copy.
 struct LowpShadow {
     uint16_t* p = nullptr;  // element i of [lo, hi) goes to p[i - lo]
     int64_t lo = 0, hi = 0;
 };
-inline thread_local LowpShadow g_lowp_shadow;
 
 // A clip + SGD left pending by the previous step (gs_trainer in deferred-update
-// mode, step.hip), applied by the next layer-1 forward launch of this thread
-// (the fp32 wide kernel), then cleared.  The step's last slab sum wrote
-// S = W1 - lr·G1, W1's update when the clip coefficient of its group is 1;
-// every workgroup of the forward folds the norm partials itself and reads S
-// as W1 when it is, else writes W1 - lr·(coef·G1) into S's buffer first.  The
-// forward's grid also applies the pending update to the flat parameters
-// [up_lo, up_hi) (W2, Wc, bc: read only after the forward).
+// mode, step.hip), applied by the layer-1 forward launch it is passed to (the
+// wide kernel).  The step's last slab sum wrote S = W1 - lr·G1, W1's update
+// when the clip coefficient of its group is 1; every workgroup of the forward
+// folds the norm partials itself and reads S as W1 when it is, else writes
+// W1 - lr·(coef·G1) into S's buffer first.  The forward's grid also applies
+// the pending update to the flat parameters [up_lo, up_hi) (W2, Wc, bc: read
+// only after the forward).
 struct FwdSpec {
     int on = 0;
     const float* S = nullptr;    // W1 - lr·G1 (clip coefficient 1)
@@ -236,9 +240,8 @@ struct FwdSpec {
     float* p = nullptr;          // flat params / grads
     float* g = nullptr;
     int64_t up_lo = 0, up_hi = 0, grp1_lo = 0;  // the other parameters; group 1 from grp1_lo
-    KStamp stamp;                // a timed launch's span (g_kernel_stamp), independent of `on`
+    KStamp stamp;                // a timed launch's span (the launcher fills it), independent of `on`
 };
-inline thread_local FwdSpec g_fwd_spec;
 
 __device__ __forceinline__ int kstamp_block() { return blockIdx.x + blockIdx.y * gridDim.x; }
 __device__ __forceinline__ void kstamp_begin(const KStamp& k) {
@@ -252,33 +255,20 @@ __device__ __forceinline__ void kstamp_end(const KStamp& k) {
     if (threadIdx.x == 0 && kstamp_block() < kStampBlocks) k.end[kstamp_block()] = __builtin_amdgcn_s_memrealtime();
 }
 
-// A launcher whose kernel stores its span: take the armed stamp, if any (the
-// next launch_k then records the kernel's name, as an event-bound one does).
-inline thread_local bool g_name_next = false;
-inline KStamp take_kernel_stamp() {
-    const KStamp k = g_kernel_stamp;
-    g_kernel_stamp = {};
-    if (k.start) {
-        g_launch_events = {};
-        g_name_next = true;
-    }
-    return k;
-}
-
 template <typename... KArgs, typename... Args>
 inline void launch_k(void (*kernel)(KArgs...), dim3 grid, dim3 block, uint32_t smem, hipStream_t st, Args... args) {
-    LaunchEvents ev = g_launch_events;
-    if (g_name_next) {
-        g_name_next = false;
-        g_launch_name = hipKernelNameRefByPtr(reinterpret_cast<const void*>(kernel), st);
-    }
-    if (ev.start) {
-        g_launch_events = {};
-        g_launch_name = hipKernelNameRefByPtr(reinterpret_cast<const void*>(kernel), st);
-        hipExtLaunchKernelGGL(kernel, grid, block, smem, st, ev.start, ev.stop, 0, static_cast<KArgs>(args)...);
-    } else {
-        kernel<<<grid, block, smem, st>>>(static_cast<KArgs>(args)...);
-    }
+    kernel<<<grid, block, smem, st>>>(static_cast<KArgs>(args)...);
+}
+
+// The launch a timer may time: records the kernel's name, and binds the
+// timer's events to the dispatch unless the kernel took the stamp.
+template <typename... KArgs, typename... Args>
+inline void launch_k(LaunchTimer* tm, void (*kernel)(KArgs...), dim3 grid, dim3 block, uint32_t smem, hipStream_t st,
+                     Args... args) {
+    if (!tm || !tm->start) return launch_k(kernel, grid, block, smem, st, args...);
+    tm->kernel = hipKernelNameRefByPtr(reinterpret_cast<const void*>(kernel), st);
+    if (tm->stamped) kernel<<<grid, block, smem, st>>>(static_cast<KArgs>(args)...);
+    else hipExtLaunchKernelGGL(kernel, grid, block, smem, st, tm->start, tm->stop, 0, static_cast<KArgs>(args)...);
 }
 
 }  // namespace gs

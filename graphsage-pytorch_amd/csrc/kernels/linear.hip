@@ -133,30 +133,22 @@ bool linear_fwd_wide_ok(gs_dtype dt, int64_t F, const void* Xs, int64_t ldxs, co
 }
 static int64_t slab_split_blocks(int64_t len) { return (len / 4 + 63) / 64; }
 
-}  // namespace gs
-
-extern "C" {
-
-int gs_sage_linear_fwd(gs_dtype dt, int64_t n, int64_t F, int64_t H, const void* Xs, int64_t ldxs,
-                       const int32_t* sidx, const void* A, int64_t lda, const void* Wd, float* out,
-                       int64_t ldo, int32_t relu, void* stream) {
-    GS_API_BEGIN
-    using namespace gs;
+void linear_fwd_launch(gs_dtype dt, int64_t n, int64_t F, int64_t H, const void* Xs, int64_t ldxs,
+                       const int32_t* sidx, const void* A, int64_t lda, const void* Wd, float* out, int64_t ldo,
+                       int32_t relu, hipStream_t st, const FwdSpec* pend, LaunchTimer* timer) {
     GS_REQUIRE(dt == GS_F32 || dt == GS_BF16, GS_EINVAL, "dtype must be f32 or bf16");
     GS_REQUIRE(n >= 0 && n < (int64_t(1) << 31) && F >= 1 && F < (1 << 28), GS_EINVAL, "bad sizes");
     GS_REQUIRE(H >= 16 && H <= 256 && H % 16 == 0, GS_EINVAL, "out_size must be a multiple of 16 in [16, 256]");
     GS_REQUIRE(lda >= F && ldo >= H && (!Xs || ldxs >= F), GS_EINVAL, "leading dimension too small");
-    GS_REQUIRE(n > 0 || !g_fwd_spec.on, GS_EINVAL, "pending update with no rows");
-    if (n == 0) return GS_OK;
+    // a pending clip + SGD (the trainer's deferred update): the wide kernel applies it
+    FwdSpec sp = pend ? *pend : FwdSpec{};
+    GS_REQUIRE(n > 0 || !sp.on, GS_EINVAL, "pending update with no rows");
+    if (n == 0) return;
     GS_REQUIRE(A && Wd && out, GS_EINVAL, "NULL device pointer");
     const bool self = Xs != nullptr;
     const int K = static_cast<int>(self ? 2 * F : F);
     const bool vload = fwd_vload(dt, F, Xs, ldxs, A, lda, Wd);
-    hipStream_t st = as_stream(stream);
     const int nn = static_cast<int>(n), ff = static_cast<int>(F), hh = static_cast<int>(H);
-    // a pending clip + SGD (the trainer's deferred update): the fp32 wide kernel applies it
-    FwdSpec sp = g_fwd_spec;
-    g_fwd_spec = {};
     GS_REQUIRE(!sp.on || ((dt == GS_F32 ? (Wd == sp.S && !sp.Wn_lp) : (Wd == sp.S_lp && sp.Wn_lp != nullptr)) &&
                           K % 4 == 0 && self && relu && sp.np0 >= 1 && sp.np0 <= 512 && sp.np1 >= 1 &&
                           sp.np1 <= 512 && sp.up_hi > sp.up_lo),
@@ -166,7 +158,7 @@ int gs_sage_linear_fwd(gs_dtype dt, int64_t n, int64_t F, int64_t H, const void*
         // in the same order, whatever the row tiling), rows balanced over one
         // workgroup per CU and column tile (FwdRows): each workgroup takes
         // base or base + 1 row tiles of 16, at most 4
-        sp.stamp = take_kernel_stamp();  // a timed launch: the kernel stores its own span
+        sp.stamp = take_stamp(timer);  // a timed launch: the kernel stores its own span
         const int64_t tiles = (n + 15) / 16, gy = (H + 63) / 64;
         int64_t groups = std::max<int64_t>(1, device_cus() / gy);
         int64_t per = (tiles + groups - 1) / groups;
@@ -187,7 +179,7 @@ int gs_sage_linear_fwd(gs_dtype dt, int64_t n, int64_t F, int64_t H, const void*
         const dim3 gw = gy == 1 ? dim3(static_cast<unsigned>(groups))
                                 : dim3(static_cast<unsigned>((groups + 7) / 8 * 8 * gy));
 #define GS_LFWDW(TT, R, SELF, RELU_, PEND)                                                                  \
-        launch_k(linear_fwd_wide_kernel<TT, R, SELF, RELU_, PEND>, gw, dim3(R * 16), 0, st, nn, ff, hh, K,   \
+        launch_k(timer, linear_fwd_wide_kernel<TT, R, SELF, RELU_, PEND>, gw, dim3(R * 16), 0, st, nn, ff, hh, K, \
                  static_cast<const TT*>(Xs), ldxs, sidx, static_cast<const TT*>(A), lda,                       \
                  static_cast<const TT*>(Wd), out, ldo, rs, sp)
 #define GS_LFWDW_R(TT, R)                                                                                \
@@ -203,12 +195,12 @@ int gs_sage_linear_fwd(gs_dtype dt, int64_t n, int64_t F, int64_t H, const void*
 #undef GS_LFWDW_R
 #undef GS_LFWDW
         check_launch("gs_sage_linear_fwd(wide)");
-        return GS_OK;
+        return;
     }
     GS_REQUIRE(!sp.on, GS_EINVAL, "pending update needs the wide forward (16-B aligned operands)");
     const dim3 grid(static_cast<unsigned>((n + 15) / 16), static_cast<unsigned>((H + 63) / 64));
 #define GS_LFWD1(TT, SELF, RELU, VL)                                                                     \
-    launch_k(linear_fwd_kernel<TT, SELF, RELU, VL>, grid, dim3(kThreads), 0, st,                        \
+    launch_k(timer, linear_fwd_kernel<TT, SELF, RELU, VL>, grid, dim3(kThreads), 0, st,                 \
         nn, ff, hh, K, static_cast<const TT*>(Xs), ldxs, sidx, static_cast<const TT*>(A), lda,          \
         static_cast<const TT*>(Wd), out, ldo)
 #define GS_LFWD_V(TT, SELF, RELU) \
@@ -224,6 +216,17 @@ int gs_sage_linear_fwd(gs_dtype dt, int64_t n, int64_t F, int64_t H, const void*
 #undef GS_LFWD_V
 #undef GS_LFWD1
     check_launch("gs_sage_linear_fwd");
+}
+
+}  // namespace gs
+
+extern "C" {
+
+int gs_sage_linear_fwd(gs_dtype dt, int64_t n, int64_t F, int64_t H, const void* Xs, int64_t ldxs,
+                       const int32_t* sidx, const void* A, int64_t lda, const void* Wd, float* out,
+                       int64_t ldo, int32_t relu, void* stream) {
+    GS_API_BEGIN
+    gs::linear_fwd_launch(dt, n, F, H, Xs, ldxs, sidx, A, lda, Wd, out, ldo, relu, gs::as_stream(stream));
     GS_API_END
 }
 
@@ -242,7 +245,7 @@ namespace gs {
 int linear_dw_slabs(gs_dtype dt, int64_t n, int64_t F, int64_t H, const void* Xs, int64_t ldxs,
                     const int32_t* sidx, const void* A, int64_t lda, const float* dout, const float* out,
                     int64_t ldo, int32_t relu, float* dW, void* ws, int64_t ws_bytes, hipStream_t st,
-                    int64_t H_split, int phases) {
+                    int64_t H_split, int phases, LaunchTimer* timer) {
     GS_REQUIRE(dt == GS_F32 || dt == GS_BF16, GS_EINVAL, "dtype must be f32 or bf16");
     GS_REQUIRE(phases == 1 || phases == 2, GS_EINVAL, "dW: 1 or 2 row phases");
     GS_REQUIRE(n >= 0 && n < (int64_t(1) << 31) && F >= 1 && H >= 1 && H <= 4096, GS_EINVAL, "bad sizes");
@@ -276,11 +279,11 @@ int linear_dw_slabs(gs_dtype dt, int64_t n, int64_t F, int64_t H, const void* Xs
     // workgroups mapped XCD by XCD: every tile of slab z on XCD z % 8 (PMC HBM
     // bytes 35.2 -> 19.4 MB per launch: dZ no longer fetched by all 8 XCDs)
     const dim3 grid_x(static_cast<unsigned>(kXcds * tiles * ((S + kXcds - 1) / kXcds)));
-    const KStamp ks = take_kernel_stamp();  // a timed launch: the kernel stores its own span
+    const KStamp ks = take_stamp(timer);  // a timed launch: the kernel stores its own span
 #define GS_LDW2(TT, SELF, RELU, VL, ZV, PH)                                                                   \
-    launch_k(linear_dw_xcd_kernel<TT, SELF, RELU, VL, ZV, PH>, grid_x, dim3(kThreads * PH), 0, st, nn, ff, hh, kk, \
-             rps, gx, tiles, S, static_cast<const TT*>(Xs), ldxs, sidx, static_cast<const TT*>(A), lda, dout, \
-             out, ldo, target, H * K, ks)
+    launch_k(timer, linear_dw_xcd_kernel<TT, SELF, RELU, VL, ZV, PH>, grid_x, dim3(kThreads * PH), 0, st, nn, ff, \
+             hh, kk, rps, gx, tiles, S, static_cast<const TT*>(Xs), ldxs, sidx, static_cast<const TT*>(A), lda, \
+             dout, out, ldo, target, H * K, ks)
 #define GS_LDW1(TT, SELF, RELU, VL, ZV) \
     do { if (phases == 2) GS_LDW2(TT, SELF, RELU, VL, ZV, 2); else GS_LDW2(TT, SELF, RELU, VL, ZV, 1); } while (0)
 #define GS_LDW_Z(TT, SELF, RELU, VL) \
@@ -321,22 +324,20 @@ bool sum_slabs_pair_ok(int64_t len1, int64_t len2) { return slab_split_on(len1) 
 int sum_slabs_pair_parts2(int64_t len2) { return static_cast<int>(slab_split_blocks(len2)); }
 
 int sum_slabs_pair_launch(const SlabSum& s1, const SlabSum& s2, hipStream_t st, const float* spec_P, float* spec_S,
-                          float lr, uint16_t* spec_S_lp) {
+                          float lr, uint16_t* spec_S_lp, DoneFlag done, LaunchTimer* timer) {
     GS_REQUIRE(slab_split_on(s1.len) && s1.S > 1 && (s2.S <= 1 || slab_split_on(s2.len)), GS_EINVAL,
                "slab pair: sums not split");
     const int nb1 = static_cast<int>(slab_split_blocks(s1.len));
     const int nb2 = s2.S > 1 ? static_cast<int>(slab_split_blocks(s2.len)) : 0;
     SlabSpec spec;
-    DoneFlag done;
+    GS_REQUIRE(spec_S || !done.ptr, GS_EINVAL, "slab pair: the done flag goes with the update");
     if (spec_S) {  // the step's last launch: it carries the done flag
         GS_REQUIRE(spec_P && aligned16(spec_P) && aligned16(spec_S), GS_EINVAL, "slab pair: bad update buffers");
         GS_REQUIRE(!spec_S_lp || reinterpret_cast<uintptr_t>(spec_S_lp) % 8 == 0, GS_EINVAL, "slab pair: bad bf16 buffer");
         spec = SlabSpec{spec_P, spec_S, lr, spec_S_lp};
-        done = g_done_flag;
-        g_done_flag = {};
     }
-    const KStamp ks = take_kernel_stamp();  // a timed launch: the kernel stores its own span
-    launch_k(sum_slabs_pair_kernel, dim3(static_cast<unsigned>(nb1 + nb2)), dim3(kSlabParts * 64), 0, st, s1, nb1, s2,
+    const KStamp ks = take_stamp(timer);  // a timed launch: the kernel stores its own span
+    launch_k(timer, sum_slabs_pair_kernel, dim3(static_cast<unsigned>(nb1 + nb2)), dim3(kSlabParts * 64), 0, st, s1, nb1, s2,
              nb2, spec, done.ptr, done.value, ks);
     check_launch("sum_slabs_pair");
     return nb1;

@@ -6,6 +6,7 @@
 #include <cstdlib>
 
 #include "cls_dev.hpp"
+#include "internal.hpp"
 
 namespace gs {
 
@@ -293,7 +294,7 @@ __global__ __launch_bounds__(kTb) void group_sumsq_spec_kernel(Groups G, const f
 }
 
 int sumsq_spec_launch(int32_t n_groups, const int64_t* goff_host, const float* grads, float* part, const float* P,
-                      float* S, uint16_t* S_lp, int64_t n1, float lr, float scale, hipStream_t st) {
+                      float* S, uint16_t* S_lp, int64_t n1, float lr, float scale, hipStream_t st, DoneFlag done) {
     GS_REQUIRE(n_groups >= 1 && n_groups <= 8 && goff_host && grads && part && P && S, GS_EINVAL, "sumsq_spec: bad args");
     GS_REQUIRE(goff_host[0] == 0 && n1 <= goff_host[1], GS_EINVAL, "sumsq_spec: W1 not at the front of group 0");
     Groups G;
@@ -301,8 +302,7 @@ int sumsq_spec_launch(int32_t n_groups, const int64_t* goff_host, const float* g
     G.pstride = kNormBlocks;
     for (int i = 0; i < n_groups; ++i) G.npart[i] = kNormBlocks;
     for (int i = 0; i <= n_groups; ++i) G.off[i] = goff_host[i];
-    const SumsqSpec sp{P, S, S_lp, n1, lr, scale, g_done_flag.ptr, g_done_flag.value};
-    g_done_flag = {};
+    const SumsqSpec sp{P, S, S_lp, n1, lr, scale, done.ptr, done.value};
     group_sumsq_spec_kernel<<<dim3(kNormBlocks, n_groups), kTb, 0, st>>>(G, grads, part, sp);
     check_launch("sumsq_spec");
     return kNormBlocks;
@@ -423,7 +423,8 @@ int cls_rows_launch(int64_t B, int64_t D, int64_t C, const float* E, const float
 }
 
 void sgd_with_parts(int32_t n_groups, const int64_t* goff_host, const int* npart, int pstride, float* params,
-                    float* grads, const float* part, float grad_scale, float max_norm, float lr, hipStream_t st) {
+                    float* grads, const float* part, float grad_scale, float max_norm, float lr, hipStream_t st,
+                    LowpShadow sh, DoneFlag done) {
     GS_REQUIRE(n_groups >= 1 && n_groups <= 8, GS_EINVAL, "1..8 parameter groups");
     Groups G;
     G.n = n_groups;
@@ -431,8 +432,6 @@ void sgd_with_parts(int32_t n_groups, const int64_t* goff_host, const int* npart
     for (int i = 0; i < n_groups; ++i) G.npart[i] = npart[i];
     for (int i = 0; i <= n_groups; ++i) G.off[i] = goff_host[i];
     const int64_t total = G.off[n_groups];
-    const LowpShadow sh = g_lowp_shadow;
-    g_lowp_shadow = {};
     G.sh = sh.p;
     G.sh_lo = sh.lo;
     G.sh_hi = sh.hi;
@@ -442,15 +441,32 @@ void sgd_with_parts(int32_t n_groups, const int64_t* goff_host, const int* npart
     if (vec) {  // 4.9 us -> see DESIGN §4 (rmat2m, ~100k parameters)
         const int64_t n4 = total / 4;
         const dim3 grid(static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>((n4 + kTb - 1) / kTb, 512))));
-        sgd4_kernel<<<grid, kTb, 0, st>>>(G, params, grads, part, grad_scale, max_norm, lr, g_done_flag.ptr,
-                                          g_done_flag.value);
+        sgd4_kernel<<<grid, kTb, 0, st>>>(G, params, grads, part, grad_scale, max_norm, lr, done.ptr, done.value);
     } else {
         const dim3 grid(static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>((total + kTb - 1) / kTb, 512))));
-        sgd_kernel<<<grid, kTb, 0, st>>>(G, params, grads, part, grad_scale, max_norm, lr, g_done_flag.ptr,
-                                         g_done_flag.value);
+        sgd_kernel<<<grid, kTb, 0, st>>>(G, params, grads, part, grad_scale, max_norm, lr, done.ptr, done.value);
     }
-    g_done_flag = {};
     check_launch("sgd");
+}
+
+void clip_sgd_launch(int32_t n_groups, const int64_t* goff_host, float* params, float* grads, float grad_scale,
+                     float max_norm, float lr, float* ws, hipStream_t st, LowpShadow sh, DoneFlag done) {
+    GS_REQUIRE(n_groups >= 1 && n_groups <= 8 && goff_host, GS_EINVAL, "1..8 parameter groups");
+    GS_REQUIRE(params && grads && ws, GS_EINVAL, "NULL device pointer");
+    Groups G;
+    G.n = n_groups;
+    G.pstride = kNormBlocks;
+    G.sh = sh.p;
+    G.sh_lo = sh.lo;
+    G.sh_hi = sh.hi;
+    for (int i = 0; i < n_groups; ++i) G.npart[i] = kNormBlocks;
+    for (int i = 0; i <= n_groups; ++i) G.off[i] = goff_host[i];
+    for (int i = 0; i < n_groups; ++i) GS_REQUIRE(G.off[i] <= G.off[i + 1], GS_EINVAL, "group offsets not sorted");
+    group_sumsq_kernel<<<dim3(kNormBlocks, n_groups), kTb, 0, st>>>(G, grads, ws);
+    const int64_t total = G.off[n_groups];
+    const dim3 grid(static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>((total + kTb - 1) / kTb, 512))));
+    sgd_kernel<<<grid, kTb, 0, st>>>(G, params, grads, ws, grad_scale, max_norm, lr, done.ptr, done.value);
+    check_launch("gs_clip_sgd");
 }
 
 }  // namespace gs
@@ -476,28 +492,7 @@ int gs_cls_nll_fwd_bwd(int64_t B, int64_t D, int64_t C, const float* E, const fl
 int gs_clip_sgd(int32_t n_groups, const int64_t* goff_host, float* params, float* grads, float grad_scale,
                 float max_norm, float lr, float* ws, void* stream) {
     GS_API_BEGIN
-    using namespace gs;
-    GS_REQUIRE(n_groups >= 1 && n_groups <= 8 && goff_host, GS_EINVAL, "1..8 parameter groups");
-    GS_REQUIRE(params && grads && ws, GS_EINVAL, "NULL device pointer");
-    const LowpShadow sh = g_lowp_shadow;
-    g_lowp_shadow = {};
-    Groups G;
-    G.n = n_groups;
-    G.pstride = kNormBlocks;
-    G.sh = sh.p;
-    G.sh_lo = sh.lo;
-    G.sh_hi = sh.hi;
-    for (int i = 0; i < n_groups; ++i) G.npart[i] = kNormBlocks;
-    for (int i = 0; i <= n_groups; ++i) G.off[i] = goff_host[i];
-    for (int i = 0; i < n_groups; ++i) GS_REQUIRE(G.off[i] <= G.off[i + 1], GS_EINVAL, "group offsets not sorted");
-    hipStream_t st = as_stream(stream);
-    group_sumsq_kernel<<<dim3(kNormBlocks, n_groups), kTb, 0, st>>>(G, grads, ws);
-    const int64_t total = G.off[n_groups];
-    const dim3 grid(static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>((total + kTb - 1) / kTb, 512))));
-    sgd_kernel<<<grid, kTb, 0, st>>>(G, params, grads, ws, grad_scale, max_norm, lr, g_done_flag.ptr,
-                                     g_done_flag.value);
-    g_done_flag = {};
-    check_launch("gs_clip_sgd");
+    gs::clip_sgd_launch(n_groups, goff_host, params, grads, grad_scale, max_norm, lr, ws, gs::as_stream(stream));
     GS_API_END
 }
 

@@ -89,7 +89,7 @@ struct gs_trainer {
     int w1_chunks = 1;
     // bf16 features: W1 in bf16 for the layer-1 forward.  Cast from the fp32
     // W1 before a forward, except inside a runner loop (lp_keep), where the
-    // SGD launch writes it beside W1 (g_lowp_shadow) and it stays valid from
+    // SGD launch writes it beside W1 (lowp_shadow below) and it stays valid from
     // one step to the next: nothing else writes the parameters there.
     uint16_t* w1_lp = nullptr;
     bool lp_keep = false, lp_valid = false;
@@ -128,6 +128,13 @@ struct gs_trainer {
         int64_t max_steps = 0, n = 0;
     } cap;
     const float* last_emb = nullptr;  // the last run_step's [B, H] top-layer output
+    // the runner's step-completion flag (trainer_set_done), until the launch that stores it is issued
+    gs::DoneFlag done;
+    gs::DoneFlag take_done() {
+        const gs::DoneFlag d = done;
+        done = {};
+        return d;
+    }
     ~gs_trainer() {
         if (w1_alt) (void)hipFree(w1_alt);
         if (w1_lp_alt) (void)hipFree(w1_lp_alt);
@@ -175,16 +182,18 @@ static inline void ok(int rc) {
     if (rc != GS_OK) fail(rc, gs_last_error());
 }
 
-// Bind the next launch_k launch to timer site `site` when it has capacity
-// left; returns whether it did (pass the result to timed_done).
-static inline bool timed_arm(gs_trainer& T, int site) {
+// The timer of site `site`'s next entry when the site has capacity left and
+// this call is one it times, else an empty one (which times nothing): pass it
+// to the launch, then to timed_done.
+static inline LaunchTimer timed_arm(gs_trainer& T, int site) {
     auto& tm = T.timer[site];
-    if (tm.n >= static_cast<int64_t>(tm.ev0.size())) return false;
-    if (++tm.calls % tm.every) return false;
-    g_launch_events = {tm.ev0[tm.n], tm.ev1[tm.n]};
-    if (tm.st0) g_kernel_stamp = {tm.st0 + tm.n * kStampBlocks, tm.st1 + tm.n * kStampBlocks};
-    g_launch_name = nullptr;  // set by the timed launch
-    return true;
+    LaunchTimer lt;
+    if (tm.n >= static_cast<int64_t>(tm.ev0.size())) return lt;
+    if (++tm.calls % tm.every) return lt;
+    lt.start = tm.ev0[tm.n];
+    lt.stop = tm.ev1[tm.n];
+    if (tm.st0) lt.stamp = {tm.st0 + tm.n * kStampBlocks, tm.st1 + tm.n * kStampBlocks};
+    return lt;
 }
 // Timer events only measure: no system-scope release when they complete (a
 // system-scope release writes back and invalidates the caches under the work
@@ -200,16 +209,48 @@ static std::string demangle(const char* sym) {
     return out;
 }
 
-static inline void timed_done(gs_trainer& T, int site, bool armed) {
-    if (!armed) return;
+static inline void timed_done(gs_trainer& T, int site, const LaunchTimer& lt) {
+    if (!lt.start) return;
     auto& tm = T.timer[site];
-    if (tm.st0) tm.stamped[tm.n] = g_kernel_stamp.start == nullptr;  // the launch took the stamp
-    g_kernel_stamp = {};
-    GS_REQUIRE(!g_launch_events.start, GS_EINVAL, "timed launch did not consume its events");
+    GS_REQUIRE(lt.kernel, GS_EINVAL, "timed launch did not reach a kernel");
+    if (tm.st0) tm.stamped[tm.n] = lt.stamped;
     // the kernel of the latest timed launch (the layer-1 forward has two instances:
     // with the deferred update pending, and without, at a run's first step)
-    if (g_launch_name) T.timer[site].kernel = demangle(g_launch_name);
-    ++T.timer[site].n;
+    tm.kernel = demangle(lt.kernel);
+    ++tm.n;
+}
+
+// Field f of hop `hop` (1-based) in a packed sample.
+static inline const int32_t* pack_field(const int32_t* pack, const int64_t* offsets, int hop, int f) {
+    const int64_t o = offsets[(hop - 1) * GS_PK_NFIELDS + f];
+    GS_REQUIRE(o >= 0, GS_EINVAL, "pack field missing");
+    return pack + o;
+}
+
+// The pending clip + SGD (gs_trainer::pending) as the launch argument of
+// whatever applies it: W1's speculative update S in the buffer that is not
+// current, the norm partials and the other parameters' range.  The layer-1
+// forward adds its recompute buffers (Wn, S_lp, Wn_lp).
+static FwdSpec pending_spec(gs_trainer& T) {
+    const gs_trainer_config& c = T.cfg;
+    FwdSpec sp;
+    sp.on = 1;
+    sp.S = T.w1_buf(T.w1_cur ^ 1);
+    sp.P = T.w1_buf(T.w1_cur);
+    sp.G1 = c.grads + T.w_off[0];
+    sp.part0 = T.pend_part;
+    sp.part1 = T.pend_part + T.pend_pstride;
+    sp.np0 = T.pend_np[0];
+    sp.np1 = T.pend_np[1];
+    sp.lr = c.lr;
+    sp.max_norm = c.max_norm;
+    sp.scale = T.pend_scale;
+    sp.p = c.params;
+    sp.g = c.grads;
+    sp.up_lo = T.w_off[0] + T.w_rows[0] * T.w_cols[0];
+    sp.up_hi = T.total;
+    sp.grp1_lo = T.cls_w_off;
+    return sp;
 }
 
 // The layer-1 gather-aggregate of one packed sample (models.py:291-330 at
@@ -219,15 +260,11 @@ static void gather1(gs_trainer& T, const int32_t* pack, const int64_t* hop_sizes
     const gs_trainer_config& c = T.cfg;
     const int L = c.n_layers;
     const int64_t F = c.feat_dim;
-    auto fld = [&](int f) -> const int32_t* {
-        const int64_t o = offsets[(L - 1) * GS_PK_NFIELDS + f];
-        GS_REQUIRE(o >= 0, GS_EINVAL, "pack field missing");
-        return pack + o;
-    };
-    const bool timed = timed_arm(T, 0);
-    ok(gs_agg_fwd(static_cast<gs_agg>(c.agg), static_cast<gs_dtype>(c.feat_dtype), c.X, c.feat_ld, F,
-                  hop_sizes[4 * (L - 1)], fld(GS_PK_POS_PTR), fld(GS_PK_POS), nullptr, c.col, fld(GS_PK_DST_IDS),
-                  c.gcn, out, static_cast<gs_dtype>(c.feat_dtype), ldo > 0 ? ldo : F, nullptr, st));
+    auto fld = [&](int f) { return pack_field(pack, offsets, L, f); };
+    LaunchTimer timed = timed_arm(T, 0);
+    agg_fwd_launch(static_cast<gs_agg>(c.agg), static_cast<gs_dtype>(c.feat_dtype), c.X, c.feat_ld, F,
+                   hop_sizes[4 * (L - 1)], fld(GS_PK_POS_PTR), fld(GS_PK_POS), nullptr, c.col, fld(GS_PK_DST_IDS),
+                   c.gcn, out, static_cast<gs_dtype>(c.feat_dtype), ldo > 0 ? ldo : F, nullptr, st, &timed);
     timed_done(T, 0, timed);
 }
 
@@ -238,11 +275,7 @@ static void gather1_ids(gs_trainer& T, const int32_t* pack, const int64_t* hop_s
                         int slot, hipStream_t st) {
     const gs_trainer_config& c = T.cfg;
     const int L = c.n_layers;
-    auto fld = [&](int f) -> const int32_t* {
-        const int64_t o = offsets[(L - 1) * GS_PK_NFIELDS + f];
-        GS_REQUIRE(o >= 0, GS_EINVAL, "pack field missing");
-        return pack + o;
-    };
+    auto fld = [&](int f) { return pack_field(pack, offsets, L, f); };
     const int64_t n_dst = hop_sizes[4 * (L - 1)];
     int32_t* ids = T.ids_slot[slot];
     const int64_t n_top = hop_sizes[0];
@@ -251,11 +284,7 @@ static void gather1_ids(gs_trainer& T, const int32_t* pack, const int64_t* hop_s
     const int64_t n_rec = hop_sizes[2];  // |L1|: hop 1's sources
     T.rec_ready[slot] = T.top_ready[slot] && T.rec_slot[slot] && n_rec <= T.rec_rows;
     if (T.top_ready[slot]) {
-        auto f1 = [&](int f) -> const int32_t* {
-            const int64_t o = offsets[f];  // hop 1
-            GS_REQUIRE(o >= 0, GS_EINVAL, "pack field missing");
-            return pack + o;
-        };
+        auto f1 = [&](int f) { return pack_field(pack, offsets, 1, f); };
         resolve_top_launch(n_dst, T.k_ids, fld(GS_PK_POS_PTR), fld(GS_PK_POS), c.col, fld(GS_PK_DST_IDS), c.gcn, ids,
                            n_top, T.top_k, f1(GS_PK_NBR_PTR), f1(GS_PK_NBR), f1(GS_PK_SELF), T.top_slot[slot], st,
                            T.rec_ready[slot] ? n_rec : 0, f1(GS_PK_TPTR), f1(GS_PK_TIDX), T.rec_slot[slot]);
@@ -263,17 +292,18 @@ static void gather1_ids(gs_trainer& T, const int32_t* pack, const int64_t* hop_s
         resolve_ids_launch(n_dst, T.k_ids, fld(GS_PK_POS_PTR), fld(GS_PK_POS), c.col, fld(GS_PK_DST_IDS), c.gcn, ids,
                            st);
     }
-    const bool timed = timed_arm(T, 0);
+    LaunchTimer timed = timed_arm(T, 0);
     if (T.self_rows) {  // [self | agg] rows
         char* base = static_cast<char*>(T.a1_slot[slot]);
         const int64_t xsz = c.feat_dtype == GS_BF16 ? 2 : 4;
         agg_ids_launch(static_cast<gs_agg>(c.agg), static_cast<gs_dtype>(c.feat_dtype), c.X, c.feat_ld, c.feat_dim,
                        n_dst, T.k_ids, ids, fld(GS_PK_DST_IDS), c.gcn, base + c.feat_dim * xsz, 2 * c.feat_dim, st,
-                       base, 2 * c.feat_dim);
+                       base, 2 * c.feat_dim, &timed);
         T.self_in_slot[slot] = true;
     } else {
         agg_ids_launch(static_cast<gs_agg>(c.agg), static_cast<gs_dtype>(c.feat_dtype), c.X, c.feat_ld, c.feat_dim,
-                       n_dst, T.k_ids, ids, fld(GS_PK_DST_IDS), c.gcn, T.a1_slot[slot], c.feat_dim, st);
+                       n_dst, T.k_ids, ids, fld(GS_PK_DST_IDS), c.gcn, T.a1_slot[slot], c.feat_dim, st, nullptr, 0,
+                       &timed);
     }
     timed_done(T, 0, timed);
 }
@@ -295,11 +325,7 @@ int64_t run_step(gs_trainer& T, const int32_t* pack, const int64_t* hop_sizes, c
     const size_t xsz = lowp ? 2 : 4;
     std::vector<HopSz> hs(L);
     for (int j = 0; j < L; ++j) hs[j] = {hop_sizes[4 * j], hop_sizes[4 * j + 1], hop_sizes[4 * j + 2], hop_sizes[4 * j + 3]};
-    auto fld = [&](int hop, int f) -> const int32_t* {  // hop 1-based
-        const int64_t o = offsets[(hop - 1) * GS_PK_NFIELDS + f];
-        GS_REQUIRE(o >= 0, GS_EINVAL, "pack field missing");
-        return pack + o;
-    };
+    auto fld = [&](int hop, int f) { return pack_field(pack, offsets, hop, f); };  // hop 1-based
     GS_REQUIRE(hs[0].n_dst == B, GS_EINVAL, "roots / hop-1 size mismatch");
     Carve cv{ws, ws_bytes};
     // ---- activations
@@ -391,44 +417,26 @@ int64_t run_step(gs_trainer& T, const int32_t* pack, const int64_t* hop_sizes, c
         trainer_defer_update(&T, true, st);
         pend = false;
     }
+    FwdSpec sp;  // the previous step's clip + SGD, applied by this step's forward launch
     if (T.defer) {
         const int wb = pend ? T.w1_cur ^ 1 : T.w1_cur;
         W1 = lowp ? static_cast<const void*>(T.lp_buf(wb)) : static_cast<const void*>(T.w1_buf(wb));
-        if (pend) {  // the previous step's clip + SGD, applied by this forward launch
-            FwdSpec sp;
-            sp.on = 1;
-            sp.S = T.w1_buf(T.w1_cur ^ 1);
-            sp.P = T.w1_buf(T.w1_cur);
+        if (pend) {
+            sp = pending_spec(T);
             sp.Wn = T.w1_buf(T.w1_cur ^ 1);
             if (lowp) {
                 sp.S_lp = T.lp_buf(T.w1_cur ^ 1);
                 sp.Wn_lp = T.lp_buf(T.w1_cur ^ 1);
             }
-            sp.G1 = G + T.w_off[0];
-            sp.part0 = T.pend_part;
-            sp.part1 = T.pend_part + T.pend_pstride;
-            sp.np0 = T.pend_np[0];
-            sp.np1 = T.pend_np[1];
-            sp.lr = c.lr;
-            sp.max_norm = c.max_norm;
-            sp.scale = T.pend_scale;
-            sp.p = P;
-            sp.g = G;
-            sp.up_lo = T.w_off[0] + T.w_rows[0] * T.w_cols[0];
-            sp.up_hi = T.total;
-            sp.grp1_lo = T.cls_w_off;
-            g_fwd_spec = sp;
         }
     }
     if (a1_slot < 0) gather1(T, pack, hop_sizes, offsets, agg[0], st);
     {
-        const bool armed = timed_arm(T, 1);
-        ok(gs_sage_linear_fwd(static_cast<gs_dtype>(c.feat_dtype), rows[0], F, H, x1, ldx1, sidx1, a1, lda1, W1, h[0],
-                              H, 1, st));
-        g_launch_events = {};  // an alternative kernel that does not time leaves it armed
-        timed_done(T, 1, armed);
-        if (pend) {  // the launch took the pending update: W1 is now the other buffer
-            GS_REQUIRE(!g_fwd_spec.on, GS_EINVAL, "the forward launch did not take the pending update");
+        LaunchTimer timed = timed_arm(T, 1);
+        linear_fwd_launch(static_cast<gs_dtype>(c.feat_dtype), rows[0], F, H, x1, ldx1, sidx1, a1, lda1, W1, h[0], H, 1,
+                          st, &sp, &timed);
+        timed_done(T, 1, timed);
+        if (pend) {  // the launch applied the pending update: W1 is now the other buffer
             T.w1_cur ^= 1;
             T.pending = false;
         }
@@ -493,7 +501,7 @@ int64_t run_step(gs_trainer& T, const int32_t* pack, const int64_t* hop_sizes, c
         if (fusable) {
             int cls_rows;
             if (top) {
-                const bool armed = timed_arm(T, 3);
+                LaunchTimer timed = timed_arm(T, 3);
                 const bool tids = a1_slot >= 0 && T.top_ready[a1_slot];
                 if (pair) {
                     top_pair_reserve(T, B, st);
@@ -502,15 +510,15 @@ int64_t run_step(gs_trainer& T, const int32_t* pack, const int64_t* hop_sizes, c
                                                 c.labels, roots, static_cast<float*>(agg[1]), am[1], h[1], demb, dIn,
                                                 dIn + din2, cls_ws, T.xch, ++T.xch_epoch == 0 ? ++T.xch_epoch : T.xch_epoch,
                                                 T.xch_fail, st, tids ? T.top_slot[a1_slot] : nullptr,
-                                                tids ? T.top_k : 0);
+                                                tids ? T.top_k : 0, &timed);
                     lb[0].din_off2 = din2;
                 } else {
                     cls_rows = top_fwd_bwd(c.agg, B, c.n_classes, h[0], fld(1, GS_PK_NBR_PTR), fld(1, GS_PK_NBR),
                                            fld(1, GS_PK_SELF), P + T.w_off[1], P + T.cls_w_off, P + T.cls_b_off,
                                            c.labels, roots, static_cast<float*>(agg[1]), am[1], h[1], demb, dIn, cls_ws,
-                                           st, tids ? T.top_slot[a1_slot] : nullptr, tids ? T.top_k : 0);
+                                           st, tids ? T.top_slot[a1_slot] : nullptr, tids ? T.top_k : 0, &timed);
                 }
-                timed_done(T, 3, armed);
+                timed_done(T, 3, timed);
                 lb[0].din_ready = true;
             } else {
                 cls_rows = cls_rows_launch(B, H, c.n_classes, h[L - 1], P + T.cls_w_off, P + T.cls_b_off, c.labels,
@@ -554,18 +562,16 @@ int64_t run_step(gs_trainer& T, const int32_t* pack, const int64_t* hop_sizes, c
                     if (Sq > 1) sum_slabs_launch(reinterpret_cast<const float*>(dw_ws), Sq, Hc * K1, dWq, nullptr, st);
                     T.w1_chunk_hook(st, T.w_off[0] + h0 * K1, Hc * K1);
                 }
-                g_launch_events = {};
                 T.npart[0] = 0;
                 T.npart[1] = 0;
                 T.norm_ready = false;
                 return cv.at;
             }
-            const bool armed = timed_arm(T, 2);
+            LaunchTimer timed = timed_arm(T, 2);
             const int S1 = linear_dw_slabs(static_cast<gs_dtype>(c.feat_dtype), rows[0], F, H, x1, ldx1, sidx1, a1,
                                            lda1, lb.back().dH, h[0], H, 0, G + T.w_off[0], dw_ws, dw_need, st, -1,
-                                           kDw1Phases);
-            g_launch_events = {};
-            timed_done(T, 2, armed);
+                                           kDw1Phases, &timed);
+            timed_done(T, 2, timed);
             const float* s1_src = S1 > 1 ? reinterpret_cast<const float*>(dw_ws) : nullptr;
             const int s1_n = S1;
             const int n_cls = cls_reduce_grid(c.n_classes, H);
@@ -576,12 +582,13 @@ int64_t run_step(gs_trainer& T, const int32_t* pack, const int64_t* hop_sizes, c
                 // itself is left to the next forward
                 const bool spec = T.defer && !T.defer_comm && parts && np + sum_slabs_grid(H * K1) <= T.pstride &&
                                   n_cls <= T.pstride;
-                const bool armed = timed_arm(T, 4);
+                LaunchTimer timed = timed_arm(T, 4);
                 np += sum_slabs_pair_launch(SlabSum{s1_src, s1_n, H * K1, G + T.w_off[0], T.norm_part + np}, d2, st,
                                             spec ? T.w1_buf(T.w1_cur) : nullptr,
                                             spec ? T.w1_buf(T.w1_cur ^ 1) : nullptr, c.lr,
-                                            spec && lowp ? T.lp_buf(T.w1_cur ^ 1) : nullptr);
-                timed_done(T, 4, armed);
+                                            spec && lowp ? T.lp_buf(T.w1_cur ^ 1) : nullptr,
+                                            spec ? T.take_done() : DoneFlag{}, &timed);
+                timed_done(T, 4, timed);
                 T.pending = spec;
                 if (spec) {
                     T.pend_part = T.norm_part;
@@ -708,23 +715,16 @@ void trainer_reserve_top(gs_trainer* t, int64_t B, int32_t tk) {
 
 int64_t trainer_w1_floats(const gs_trainer* t) { return t->w_rows[0] * t->w_cols[0]; }
 
-}  // namespace gs
+void trainer_set_done(gs_trainer* t, int64_t* ptr, int64_t value) { t->done = {ptr, value}; }
+bool trainer_done_taken(const gs_trainer* t) { return t->done.ptr == nullptr; }
 
-namespace {
-// The SGD launch that follows also writes the bf16 W1 (runner loops only).
-struct ShadowArm {
-    gs_trainer* t;
-    explicit ShadowArm(gs_trainer* t_) : t(t_) {
-        t->lp_valid = false;
-        if (t->lp_keep && t->w1_lp)
-            gs::g_lowp_shadow = {t->w1_lp, t->w_off[0], t->w_off[0] + t->w_rows[0] * t->w_cols[0]};
-    }
-    void done() { t->lp_valid = t->lp_keep && t->w1_lp; }
-    ~ShadowArm() { gs::g_lowp_shadow = {}; }
-};
-}  // namespace
+// The bf16 W1 that an SGD launch writes beside the update (runner loops
+// only: lp_keep), passed to that launch; empty otherwise.
+static LowpShadow lowp_shadow(const gs_trainer* t) {
+    if (!(t->lp_keep && t->w1_lp)) return {};
+    return {t->w1_lp, t->w_off[0], t->w_off[0] + t->w_rows[0] * t->w_cols[0]};
+}
 
-namespace gs {
 void trainer_keep_lowp(gs_trainer* t, bool keep) {
     t->lp_keep = keep;
     t->lp_valid = false;
@@ -745,24 +745,7 @@ static void w1_home(gs_trainer* t, hipStream_t st) {
 bool trainer_defer_update(gs_trainer* t, bool on, hipStream_t st, bool comm) {
     if (!on) {
         if (t->pending) {  // the last step's clip + SGD: the flat params become what sgd4 would leave
-            FwdSpec sp;
-            sp.on = 1;
-            sp.S = t->w1_buf(t->w1_cur ^ 1);
-            sp.P = t->w1_buf(t->w1_cur);
-            sp.G1 = t->cfg.grads + t->w_off[0];
-            sp.part0 = t->pend_part;
-            sp.part1 = t->pend_part + t->pend_pstride;
-            sp.np0 = t->pend_np[0];
-            sp.np1 = t->pend_np[1];
-            sp.lr = t->cfg.lr;
-            sp.max_norm = t->cfg.max_norm;
-            sp.scale = t->pend_scale;
-            sp.p = t->cfg.params;
-            sp.g = t->cfg.grads;
-            sp.up_lo = t->w_off[0] + t->w_rows[0] * t->w_cols[0];
-            sp.up_hi = t->total;
-            sp.grp1_lo = t->cls_w_off;
-            spec_finalize_launch(sp, t->w1_buf(0), t->w_rows[0] * t->w_cols[0], st);
+            spec_finalize_launch(pending_spec(*t), t->w1_buf(0), t->w_rows[0] * t->w_cols[0], st);
             t->pending = false;
             t->w1_cur = 0;
         }
@@ -1023,20 +1006,25 @@ int gs_trainer_time_kernels_every(gs_trainer* t, int32_t site_mask, int64_t capa
 
 int gs_trainer_time_agg(gs_trainer* t, int64_t capacity) { return gs_trainer_time_kernels(t, 1, capacity); }
 
+// The stamps of a site's first n timed launches (kStampBlocks starts and ends
+// each), once everything issued has finished.
+static bool read_stamps(const gs_trainer::Timer& tm, int64_t n, std::vector<unsigned long long>& a,
+                        std::vector<unsigned long long>& b) {
+    const size_t words = static_cast<size_t>(n) * gs::kStampBlocks;
+    a.resize(words);
+    b.resize(words);
+    return hipDeviceSynchronize() == hipSuccess &&
+           hipMemcpy(a.data(), tm.st0, words * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess &&
+           hipMemcpy(b.data(), tm.st1, words * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess;
+}
+
 int64_t gs_trainer_kernel_times(gs_trainer* t, int32_t site, float* ms, int64_t cap) {
     if (!t || !ms || site < 0 || site >= gs_trainer::kSites) return -1;
     auto& tm = t->timer[site];
     const int64_t n = std::min(cap, tm.n);
     std::vector<unsigned long long> a, b;
     const int64_t W = gs::kStampBlocks;
-    if (tm.st0 && n > 0) {
-        if (hipDeviceSynchronize() != hipSuccess) return -1;
-        a.resize(n * W);
-        b.resize(n * W);
-        if (hipMemcpy(a.data(), tm.st0, n * W * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(b.data(), tm.st1, n * W * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess)
-            return -1;
-    }
+    if (tm.st0 && n > 0 && !read_stamps(tm, n, a, b)) return -1;
     for (int64_t i = 0; i < n; ++i) {
         if (tm.st0 && tm.stamped[i]) {  // the kernel's own span: min start .. max end, 100 MHz ticks
             unsigned long long lo = ~0ull, hi = 0;
@@ -1076,11 +1064,8 @@ int64_t gs_trainer_kernel_block_stats(gs_trainer* t, int32_t site, float* us4, i
         std::fill(us4, us4 + 4 * n, -1.f);
         return n;
     }
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    std::vector<unsigned long long> a(n * W), b(n * W);
-    if (hipMemcpy(a.data(), tm.st0, n * W * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(b.data(), tm.st1, n * W * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess)
-        return -1;
+    std::vector<unsigned long long> a, b;
+    if (!read_stamps(tm, n, a, b)) return -1;
     for (int64_t i = 0; i < n; ++i) {
         float* o = us4 + 4 * i;
         o[0] = o[1] = o[2] = o[3] = -1.f;
@@ -1124,16 +1109,16 @@ int gs_trainer_update_local(gs_trainer* t, void* stream) {
     }
     gs::w1_home(t, gs::as_stream(stream));  // a deferred-update step that could not defer
     const int64_t goff[3] = {0, t->cls_w_off, t->total};
-    ShadowArm arm(t);
+    t->lp_valid = false;
+    const gs::LowpShadow shadow = gs::lowp_shadow(t);
     if (t->norm_ready) {
         gs::sgd_with_parts(2, goff, t->npart, t->pstride, t->cfg.params, t->cfg.grads, t->norm_part, 1.0f,
-                           t->cfg.max_norm, t->cfg.lr, gs::as_stream(stream));
+                           t->cfg.max_norm, t->cfg.lr, gs::as_stream(stream), shadow, t->take_done());
     } else {
-        const int rc = gs_clip_sgd(2, goff, t->cfg.params, t->cfg.grads, 1.0f, t->cfg.max_norm, t->cfg.lr,
-                                   t->norm_part, stream);
-        if (rc != GS_OK) return rc;
+        gs::clip_sgd_launch(2, goff, t->cfg.params, t->cfg.grads, 1.0f, t->cfg.max_norm, t->cfg.lr, t->norm_part,
+                            gs::as_stream(stream), shadow, t->take_done());
     }
-    arm.done();
+    t->lp_valid = shadow.p != nullptr;
     t->norm_ready = false;
     GS_API_END
 }
@@ -1152,7 +1137,7 @@ int gs_trainer_update(gs_trainer* t, float grad_scale, float* ws, void* stream) 
         const bool lowp = t->cfg.feat_dtype == GS_BF16;
         const int np = gs::sumsq_spec_launch(2, goff, t->cfg.grads, ws, t->w1_buf(t->w1_cur), t->w1_buf(t->w1_cur ^ 1),
                                              lowp ? t->lp_buf(t->w1_cur ^ 1) : nullptr, n1, t->cfg.lr, grad_scale,
-                                             gs::as_stream(stream));
+                                             gs::as_stream(stream), t->take_done());
         t->pending = true;
         t->pend_part = ws;
         t->pend_pstride = np;
@@ -1163,10 +1148,11 @@ int gs_trainer_update(gs_trainer* t, float grad_scale, float* ws, void* stream) 
     }
     gs::w1_home(t, gs::as_stream(stream));
     const int64_t goff[3] = {0, t->cls_w_off, t->total};
-    ShadowArm arm(t);
-    int rc = gs_clip_sgd(2, goff, t->cfg.params, t->cfg.grads, grad_scale, t->cfg.max_norm, t->cfg.lr, ws, stream);
-    if (rc != GS_OK) return rc;
-    arm.done();
+    t->lp_valid = false;
+    const gs::LowpShadow shadow = gs::lowp_shadow(t);
+    gs::clip_sgd_launch(2, goff, t->cfg.params, t->cfg.grads, grad_scale, t->cfg.max_norm, t->cfg.lr, ws,
+                        gs::as_stream(stream), shadow, t->take_done());
+    t->lp_valid = shadow.p != nullptr;
     GS_API_END
 }
 

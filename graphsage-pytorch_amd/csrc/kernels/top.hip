@@ -64,7 +64,7 @@ struct TopArgs {
     float* slab;         // classifier partials, one [C][H+1] + 1 slab per block
     const int* tids;     // optional: per root [self | list padded to tk with -1] (resolve_top_launch)
     int tk;
-    KStamp stamp;        // a timed launch's span (g_kernel_stamp)
+    KStamp stamp;        // a timed launch's span (LaunchTimer, kcommon.hpp)
 };
 
 // The stages hand each other LDS only: lds_barrier() (kcommon.hpp), not
@@ -990,7 +990,7 @@ int top_pair_fwd_bwd(int agg, int64_t B, int64_t C, const float* Hprev, const in
                      const int32_t* self, const float* W, const float* Wc, const float* bc, const int32_t* labels,
                      const int32_t* roots, float* aggo, int32_t* argmax, float* E, float* dZ, float* dIn, float* dIn2,
                      float* slab, unsigned long long* xch, unsigned epoch, unsigned* fail, hipStream_t st,
-                     const int32_t* tids, int tk) {
+                     const int32_t* tids, int tk, LaunchTimer* timer) {
     GS_REQUIRE(B >= 1 && B < (int64_t(1) << 30) && C >= 1 && C <= 16 && epoch != 0 && xch && fail, GS_EINVAL,
                "top pair: bad arguments");
     GS_REQUIRE(!tids || (tk >= 1 && tk <= 31), GS_EINVAL, "top: padded lists need 1 <= tk <= 31");
@@ -1000,12 +1000,12 @@ int top_pair_fwd_bwd(int agg, int64_t B, int64_t C, const float* Hprev, const in
     GS_REQUIRE(top_pair_lds_ready(), GS_EHIP, "top pair: LDS limit refused");
     const size_t smem = top_pair_smem_bytes();
     TopPairArgs pa{TopArgs{static_cast<int>(B), static_cast<int>(C), Hprev, ptr, nbr, self, W, Wc, bc, labels, roots,
-                           aggo, argmax, E, dZ, dIn, slab, tids, tids ? tk : 0, take_kernel_stamp()},
+                           aggo, argmax, E, dZ, dIn, slab, tids, tids ? tk : 0, take_stamp(timer)},
                    dIn2, xch, epoch, fail};
     const int64_t quads = (B + kTopRows - 1) / kTopRows;
     const dim3 grid(static_cast<unsigned>(16 * ((quads + 7) / 8)));
-    if (agg == GS_AGG_MEAN) launch_k(sage_top_pair_kernel<GS_AGG_MEAN>, grid, dim3(kTopThreads), smem, st, pa);
-    else launch_k(sage_top_pair_kernel<GS_AGG_MAX>, grid, dim3(kTopThreads), smem, st, pa);
+    if (agg == GS_AGG_MEAN) launch_k(timer, sage_top_pair_kernel<GS_AGG_MEAN>, grid, dim3(kTopThreads), smem, st, pa);
+    else launch_k(timer, sage_top_pair_kernel<GS_AGG_MAX>, grid, dim3(kTopThreads), smem, st, pa);
     check_launch("sage_top_pair");
     return static_cast<int>(quads);
 }
@@ -1047,23 +1047,23 @@ bool top_supported(int64_t H, int64_t C, bool gcn) {
 int top_fwd_bwd(int agg, int64_t B, int64_t C, const float* Hprev, const int32_t* ptr, const int32_t* nbr,
                 const int32_t* self, const float* W, const float* Wc, const float* bc, const int32_t* labels,
                 const int32_t* roots, float* aggo, int32_t* argmax, float* E, float* dZ, float* dIn, float* slab,
-                hipStream_t st, const int32_t* tids, int tk) {
+                hipStream_t st, const int32_t* tids, int tk, LaunchTimer* timer) {
     GS_REQUIRE(B >= 1 && B < (int64_t(1) << 30) && C >= 1 && C <= kTopMaxC, GS_EINVAL, "top: bad sizes");
     GS_REQUIRE(!tids || (tk >= 1 && tk <= 31), GS_EINVAL, "top: padded lists need 1 <= tk <= 31");
     GS_REQUIRE(aligned16(Hprev) && aligned16(W) && aligned16(Wc) && aligned16(aggo) && aligned16(E) && aligned16(dZ) &&
                    aligned16(dIn) && (agg == GS_AGG_MEAN || (argmax && aligned16(argmax))),
                GS_EINVAL, "top: unaligned operand");
     TopArgs a{static_cast<int>(B), static_cast<int>(C), Hprev, ptr, nbr, self, W, Wc, bc, labels, roots,
-              aggo, argmax, E, dZ, dIn, slab, tids, tids ? tk : 0, take_kernel_stamp()};
+              aggo, argmax, E, dZ, dIn, slab, tids, tids ? tk : 0, take_stamp(timer)};
     const dim3 grid(static_cast<unsigned>((B + kTopRows - 1) / kTopRows));
     const size_t smem = top_smem_bytes(C);
     const bool small = C <= 16;
     if (agg == GS_AGG_MEAN) {
-        if (small) launch_k(sage_top_kernel<GS_AGG_MEAN, true>, grid, dim3(kTopThreads), smem, st, a);
-        else launch_k(sage_top_kernel<GS_AGG_MEAN, false>, grid, dim3(kTopThreads), smem, st, a);
+        if (small) launch_k(timer, sage_top_kernel<GS_AGG_MEAN, true>, grid, dim3(kTopThreads), smem, st, a);
+        else launch_k(timer, sage_top_kernel<GS_AGG_MEAN, false>, grid, dim3(kTopThreads), smem, st, a);
     } else {
-        if (small) launch_k(sage_top_kernel<GS_AGG_MAX, true>, grid, dim3(kTopThreads), smem, st, a);
-        else launch_k(sage_top_kernel<GS_AGG_MAX, false>, grid, dim3(kTopThreads), smem, st, a);
+        if (small) launch_k(timer, sage_top_kernel<GS_AGG_MAX, true>, grid, dim3(kTopThreads), smem, st, a);
+        else launch_k(timer, sage_top_kernel<GS_AGG_MAX, false>, grid, dim3(kTopThreads), smem, st, a);
     }
     check_launch("sage_top");
     return static_cast<int>(grid.x);

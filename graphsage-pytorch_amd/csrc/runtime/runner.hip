@@ -820,7 +820,7 @@ int gs_runner_run(gs_runner* r, int64_t n_steps, float* loss, void* stream) {
         hipStream_t st;
         bool armed = true;
         ~Unwind() {
-            gs::g_done_flag = {};  // never left for a later SGD launch of this thread
+            gs::trainer_set_done(r->cfg.trainer, nullptr, 0);  // never left for a later step of this trainer
             if (!armed) return;
             for (int k = 0; k < gs_runner::kDev; ++k)
                 if (r->flag_step[k] >= 0 && hipEventRecord(r->dev_done[k], st) == hipSuccess) {
@@ -917,7 +917,7 @@ int gs_runner_run(gs_runner* r, int64_t n_steps, float* loss, void* stream) {
         } else {
             // the done flag goes to the step's SGD launch: the fused slab sum
             // inside the step, or gs_trainer_update* below
-            if (r->use_flag) g_done_flag = {r->done_dev, b};
+            if (r->use_flag) trainer_set_done(r->cfg.trainer, r->done_dev, b);
             r->w1_issued = 0;
             int rc = gs_trainer_forward_backward_gathered(r->cfg.trainer, pk, hop_sizes, offsets,
                                                           pk + pack_total, r->cfg.batch, k, r->ws, r->ws_bytes, loss,
@@ -947,8 +947,8 @@ int gs_runner_run(gs_runner* r, int64_t n_steps, float* loss, void* stream) {
             rc = r->cfg.comm
                      ? gs_trainer_update(r->cfg.trainer, 1.0f / static_cast<float>(r->cfg.world), r->clip_ws, st)
                      : gs_trainer_update_local(r->cfg.trainer, st);
-            consumed_flag = r->use_flag && g_done_flag.ptr == nullptr;
-            g_done_flag = {};
+            consumed_flag = r->use_flag && trainer_done_taken(r->cfg.trainer);
+            trainer_set_done(r->cfg.trainer, nullptr, 0);
             if (rc != GS_OK) fail(rc, gs_last_error());
         }
         if (consumed_flag) {

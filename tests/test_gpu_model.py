@@ -724,6 +724,34 @@ def test_kernel_timer_sites_strided(gs, every):
     runner.close()
 
 
+def test_kernel_timer_event_fallback(gs):
+    """A timed layer-1 forward whose kernel stores no span of its own: with
+    F = 30 (no multiple of 4) the forward is linear_fwd_kernel, not the wide
+    self-stamping one, so site 1 is timed by the events bound to its dispatch:
+    positive durations, the kernel's name, and no per-workgroup statistics."""
+    lib = gs._lib.lib()
+    graph, g, n = _graph(gs, "rmat")
+    X = torch.from_numpy(uniform_features(5, n, 30)).to(DEV)
+    labels = torch.from_numpy((np.arange(n) % 16).astype(np.int32)).to(DEV)
+    t = train.NativeTrainer(graph, X, labels, 16, fanouts=(5, 3), seed=824)
+    gs._lib.check(lib.gs_trainer_time_kernels(t._h, 0b10, 3))
+    rng = gs.RNG(824)
+    for roots in list(train.rank_batches(np.nonzero(graph.degrees())[0], 48, 0, 1, 9))[:3]:
+        ds = models.DeviceSample(gs.sample(graph, rng, roots, [5, 3]), DEV)
+        t.forward_backward(ds, torch.from_numpy(roots.astype(np.int32)).to(DEV))
+        t.apply_update()
+    torch.cuda.synchronize()
+    out = np.zeros(3, np.float32)
+    got = int(lib.gs_trainer_kernel_times(t._h, 1, out.ctypes.data, 3))
+    name = lib.gs_trainer_kernel_name(t._h, 1).decode()
+    st = np.zeros((3, 4), np.float32)
+    n_st = int(lib.gs_trainer_kernel_block_stats(t._h, 1, st.ctypes.data, 3))
+    print("site 1:", got, out, name, n_st, st.tolist())
+    assert got == 3 and (out > 0).all(), (got, out)
+    assert "linear_fwd_kernel" in name, name
+    assert n_st == 3 and (st == -1).all(), st
+
+
 @pytest.mark.parametrize("name,gcn,fanouts,agg", [("cora", False, [10, 10], "MEAN"), ("pubmed", False, [10, 10], "MEAN"),
                                                   ("rmat", True, [25, 10], "MEAN"), ("rmat", False, [5, 4, 3], "MAX"),
                                                   ("pubmed", False, [10, 10], "MAX")])

@@ -78,7 +78,7 @@ struct TopArgs {
     float* slab;         // classifier partials, one [C][H+1] + 1 slab per block
     const int* tids;     // optional: per root [self | list padded to tk with -1] (resolve_top_launch)
     int tk;
-    KStamp stamp;        // a timed launch's span (g_kernel_stamp)
+    KStamp stamp;        // a timed launch's span (empty here: the lab times with events of its own)
 };
 
 // k offset of step i (0..15) inside a 16-wide block: the MFMA kernels' order.
@@ -534,7 +534,7 @@ int top_fwd_bwd(int agg, int64_t B, int64_t C, const float* Hprev, const int32_t
                    aligned16(dIn) && (agg == GS_AGG_MEAN || (argmax && aligned16(argmax))),
                GS_EINVAL, "top: unaligned operand");
     TopArgs a{static_cast<int>(B), static_cast<int>(C), Hprev, ptr, nbr, self, W, Wc, bc, labels, roots,
-              aggo, argmax, E, dZ, dIn, slab, tids, tids ? tk : 0, take_kernel_stamp()};
+              aggo, argmax, E, dZ, dIn, slab, tids, tids ? tk : 0, KStamp{}};
     const dim3 grid(static_cast<unsigned>((B + kTopRows - 1) / kTopRows));
     const size_t smem = top_smem_bytes(C);
     if (agg == GS_AGG_MEAN) launch_k(sage_top_kernel<GS_AGG_MEAN, kTopThreads>, grid, dim3(kTopThreads), smem, st, a);
