@@ -26,6 +26,8 @@ GS_F32, GS_BF16 = 0, 1
 GS_AGG_MEAN, GS_AGG_MAX = 0, 1
 GS_SAMPLE_GCN, GS_SAMPLE_FULL = 1, 2
 GS_DSAMPLER_NO_AUX = 8  # gs_dsampler_create: every kernel on the caller's stream
+GS_DSAMPLER_FAST = 16   # gs_dsampler_create: the counter-based (Philox) sampler
+GS_SAMPLE_FAIL_EMPTY = 4
 GS_MAX_HOPS = 8
 GS_TOPT_FUSED_BWD, GS_TOPT_TOP_LAUNCH, GS_TOPT_SELF_ROWS, GS_TOPT_DEFER_UPDATE, GS_TOPT_TOP_PAIR = range(5)
 (GS_PK_POS_PTR, GS_PK_POS, GS_PK_DST_IDS, GS_PK_NBR_PTR, GS_PK_NBR, GS_PK_SELF,
@@ -86,6 +88,8 @@ _SIGS = {
     "gs_sample_pack_bound_multi": (_i64, [_vp, _i64, _i64, _vp, _i32]),
     "gs_sample_pack_run_multi": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _i32, _vp, _i64, _vp, _vp,
                                         _p(_i64)]),
+    "gs_fsample_pack_run": (_i32, [_vp, _u64, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _p(_i64)]),
+    "gs_philox4x32": (_i32, [_vp, _vp, _vp]),
     "gs_team_create": (_i32, [_i32, _p(_vp)]),
     "gs_team_create_shared": (_i32, [_vp, _p(_vp)]),
     "gs_team_destroy": (None, [_vp]),
@@ -170,6 +174,8 @@ _SIGS = {
     "gs_dsampler_runs": (_i64, [_vp]),
     "gs_dsampler_result_of": (_i32, [_vp, _i64, _vp, _vp, _p(_i64)]),
     "gs_dsampler_debug": (_i32, [_vp, _vp, _i32]),
+    "gs_dsampler_set_seed": (_i32, [_vp, _u64]),
+    "gs_dsampler_run_at": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp]),
 }
 
 
@@ -188,7 +194,7 @@ class RunnerConfig(ctypes.Structure):
         ("fanouts", _vp), ("n_hops", _i32), ("flags", _i32), ("n_streams", _i32), ("rngs", _vp),
         ("depth", _i32), ("comm", _vp), ("world", _i32), ("embed_out", _vp), ("embed_ld", _i64),
         ("merge", _i32), ("hold", _i32), ("ar_buckets", _i32), ("helpers", _i32), ("warm", _i32),
-        ("device_sampler", _i32),
+        ("device_sampler", _i32), ("sampler_seed", _u64),
     ]
 
 

@@ -35,6 +35,7 @@
 #include "../host/graph.hpp"
 #include "../host/mt19937.hpp"
 #include "dsample.hpp"
+#include "fsample.hpp"
 
 namespace gs {
 namespace ds {
@@ -968,6 +969,7 @@ int r_of(int k) { return k > 0 ? std::max(1, 256 / k) : 256; }
 }  // namespace
 
 struct gs_dsampler {
+    gs::fs::Fast* fast = nullptr;  // GS_DSAMPLER_FAST: the counter-based sampler (fsample.hip); nothing below is used
     int32_t n_hops = 0;
     int32_t fanouts[GS_MAX_HOPS] = {};
     int32_t flags = 0;
@@ -1006,6 +1008,7 @@ struct gs_dsampler {
         return static_cast<T*>(p);
     }
     ~gs_dsampler() {
+        if (fast) gs::fs::fast_destroy(fast);
         if (done) (void)hipEventSynchronize(done);
         if (aux) (void)hipStreamSynchronize(aux);
         for (hipEvent_t e : {ev_gen, ev_join})
@@ -1102,6 +1105,7 @@ void check_status(int status) {
 
 namespace gs {
 bool dsampler_run_ready(gs_dsampler* ds, int64_t run) {
+    if (ds && ds->fast) return gs::fs::fast_run_ready(ds->fast, run);
     if (!ds || run < ds->n_runs - kResSlots) return true;
     if (run >= ds->n_runs) return false;
     const hipError_t e = hipEventQuery(ds->run_done[run % kResSlots]);
@@ -1110,6 +1114,7 @@ bool dsampler_run_ready(gs_dsampler* ds, int64_t run) {
     return true;
 }
 bool dsampler_ready(gs_dsampler* ds) {
+    if (ds && ds->fast) return gs::fs::fast_run_ready(ds->fast, -1);
     if (!ds || !ds->ran) return true;
     const hipError_t e = hipEventQuery(ds->done);
     if (e == hipErrorNotReady) return false;
@@ -1124,6 +1129,12 @@ int gs_dsampler_create(const gs_graph* gp, const int32_t* fanouts, int32_t n_hop
                        gs_dsampler** out) {
     GS_API_BEGIN
     GS_REQUIRE(gp && out, GS_EINVAL, "NULL argument");
+    if (flags & GS_DSAMPLER_FAST) {  // no MT19937 rings, no aux stream: a handle around a gs::fs::Fast
+        std::unique_ptr<gs_dsampler> fd(new gs_dsampler());
+        fd->fast = gs::fs::fast_create(gp, fanouts, n_hops, max_roots, flags);
+        *out = fd.release();
+        return GS_OK;
+    }
     GS_REQUIRE(n_hops >= 1 && n_hops <= GS_MAX_HOPS, GS_EINVAL, "n_hops out of [1, 8]");
     GS_REQUIRE(max_roots >= 1 && max_roots < (int64_t(1) << 24), GS_EINVAL, "max_roots out of range");
     const auto& g = *reinterpret_cast<const gs::Graph*>(gp);
@@ -1235,6 +1246,7 @@ void gs_dsampler_destroy(gs_dsampler* ds) { delete ds; }
 int gs_dsampler_set_rng(gs_dsampler* ds, const uint32_t* mt624, int64_t pos, void* stream) {
     GS_API_BEGIN
     GS_REQUIRE(ds && mt624, GS_EINVAL, "NULL argument");
+    GS_REQUIRE(!ds->fast, GS_EINVAL, "a GS_DSAMPLER_FAST handle has no MT19937 stream");
     GS_REQUIRE(pos >= 0 && pos <= 624, GS_EINVAL, "state index out of range");
     hipStream_t st = gs::as_stream(stream);
     if (ds->ran) hip_ok(hipEventSynchronize(ds->done), "hipEventSynchronize");
@@ -1249,6 +1261,7 @@ int gs_dsampler_set_rng(gs_dsampler* ds, const uint32_t* mt624, int64_t pos, voi
 int gs_dsampler_get_rng(gs_dsampler* ds, uint32_t* mt624, int64_t* pos, void* stream) {
     GS_API_BEGIN
     GS_REQUIRE(ds && mt624 && pos, GS_EINVAL, "NULL argument");
+    GS_REQUIRE(!ds->fast, GS_EINVAL, "a GS_DSAMPLER_FAST handle has no MT19937 stream");
     hipStream_t st = gs::as_stream(stream);
     if (ds->ran) hip_ok(hipEventSynchronize(ds->done), "hipEventSynchronize");
     const int64_t p = pos_now(ds, st);
@@ -1271,6 +1284,7 @@ int gs_dsampler_get_rng(gs_dsampler* ds, uint32_t* mt624, int64_t* pos, void* st
 int gs_dsampler_words(gs_dsampler* ds, int64_t n, uint32_t* out, void* stream) {
     GS_API_BEGIN
     GS_REQUIRE(ds && out && n >= 0 && n < kRing / 2, GS_EINVAL, "bad arguments");
+    GS_REQUIRE(!ds->fast, GS_EINVAL, "a GS_DSAMPLER_FAST handle has no MT19937 stream");
     hipStream_t st = gs::as_stream(stream);
     if (ds->ran) hip_ok(hipEventSynchronize(ds->done), "hipEventSynchronize");
     const int64_t p = pos_now(ds, st);
@@ -1285,6 +1299,7 @@ int gs_dsampler_words(gs_dsampler* ds, int64_t n, uint32_t* out, void* stream) {
 }
 
 int64_t gs_dsampler_pack_bound(const gs_dsampler* ds, int64_t n_roots) {
+    if (ds && ds->fast) return gs::fs::fast_pack_bound(ds->fast, n_roots);
     if (!ds || n_roots < 1 || n_roots > ds->max_roots) return -1;
     return gs_sample_pack_bound(ds->host_graph, n_roots, ds->fanouts, ds->n_hops) + n_roots;
 }
@@ -1292,6 +1307,7 @@ int64_t gs_dsampler_pack_bound(const gs_dsampler* ds, int64_t n_roots) {
 int gs_dsampler_run(gs_dsampler* ds, const int32_t* roots, int64_t n_roots, int32_t* pack, int64_t cap, void* stream) {
     GS_API_BEGIN
     GS_REQUIRE(ds && roots && pack, GS_EINVAL, "NULL argument");
+    GS_REQUIRE(!ds->fast, GS_EINVAL, "a GS_DSAMPLER_FAST handle samples with gs_dsampler_run_at");
     GS_REQUIRE(n_roots >= 1 && n_roots <= ds->max_roots, GS_EINVAL, "n_roots out of [1, max_roots]");
     GS_REQUIRE(cap >= gs_dsampler_pack_bound(ds, n_roots), GS_EINVAL, "pack buffer below gs_dsampler_pack_bound");
     hipStream_t st = gs::as_stream(stream);
@@ -1323,7 +1339,7 @@ int gs_dsampler_run(gs_dsampler* ds, const int32_t* roots, int64_t n_roots, int3
 
 int gs_dsampler_debug(gs_dsampler* ds, int64_t* out, int32_t n) {
     GS_API_BEGIN
-    GS_REQUIRE(ds && ds->ran && out && n >= 0 && n <= 64, GS_EINVAL, "bad arguments");
+    GS_REQUIRE(ds && !ds->fast && ds->ran && out && n >= 0 && n <= 64, GS_EINVAL, "bad arguments");
     hip_ok(hipEventSynchronize(ds->done), "hipEventSynchronize");
     std::memcpy(out, ds->ctl_host[(ds->n_runs - 1) % kResSlots].dbg, n * sizeof(int64_t));
     GS_API_END
@@ -1355,17 +1371,45 @@ void report(const gs_dsampler* ds, const Ctl& c, int64_t* hop_sizes, int64_t* of
 
 int gs_dsampler_result(gs_dsampler* ds, int64_t* hop_sizes, int64_t* offsets, int64_t* used) {
     GS_API_BEGIN
-    GS_REQUIRE(ds && ds->ran, GS_EINVAL, "no run to report");
+    GS_REQUIRE(ds, GS_EINVAL, "NULL argument");
+    if (ds->fast) {
+        gs::fs::fast_result_of(ds->fast, -1, hop_sizes, offsets, used);
+        return GS_OK;
+    }
+    GS_REQUIRE(ds->ran, GS_EINVAL, "no run to report");
     hip_ok(hipEventSynchronize(ds->done), "hipEventSynchronize");
     report(ds, ds->ctl_host[(ds->n_runs - 1) % kResSlots], hop_sizes, offsets, used);
     GS_API_END
 }
 
-int64_t gs_dsampler_runs(const gs_dsampler* ds) { return ds ? ds->n_runs : -1; }
+int64_t gs_dsampler_runs(const gs_dsampler* ds) {
+    if (ds && ds->fast) return gs::fs::fast_runs(ds->fast);
+    return ds ? ds->n_runs : -1;
+}
+
+int gs_dsampler_set_seed(gs_dsampler* ds, uint64_t seed) {
+    GS_API_BEGIN
+    GS_REQUIRE(ds && ds->fast, GS_EINVAL, "not a GS_DSAMPLER_FAST handle");
+    gs::fs::fast_set_seed(ds->fast, seed);
+    GS_API_END
+}
+
+int gs_dsampler_run_at(gs_dsampler* ds, int64_t batch_index, const int32_t* roots, int64_t n_roots, int32_t* pack,
+                       int64_t cap, void* stream) {
+    GS_API_BEGIN
+    GS_REQUIRE(ds && ds->fast, GS_EINVAL, "not a GS_DSAMPLER_FAST handle");
+    gs::fs::fast_run_at(ds->fast, batch_index, roots, n_roots, pack, cap, gs::as_stream(stream));
+    GS_API_END
+}
 
 int gs_dsampler_result_of(gs_dsampler* ds, int64_t run, int64_t* hop_sizes, int64_t* offsets, int64_t* used) {
     GS_API_BEGIN
     GS_REQUIRE(ds, GS_EINVAL, "NULL argument");
+    if (ds->fast) {
+        GS_REQUIRE(run >= 0, GS_ERANGE, "device sampler: run not issued");
+        gs::fs::fast_result_of(ds->fast, run, hop_sizes, offsets, used);
+        return GS_OK;
+    }
     GS_REQUIRE(run >= 0 && run < ds->n_runs && run >= ds->n_runs - kResSlots, GS_ERANGE,
                "device sampler: run not issued or no longer kept (the last " + std::to_string(kResSlots) +
                    " runs are)");

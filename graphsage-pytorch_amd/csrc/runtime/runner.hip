@@ -220,6 +220,7 @@ struct gs_runner {
         double sample_s = 0;
     };
     bool devmode = false;
+    bool fastmode = false;  // devmode with the counter-based sampler (cfg.device_sampler == 2): no rng streams
     // guards dstreams' queues (nq, qb, next, counted): gs_runner_release and
     // gs_runner_progress may be called from another thread than gs_runner_run
     std::recursive_mutex dev_mu;
@@ -368,7 +369,11 @@ void gs_runner::dev_enqueue(int w) {
         if (b >= n_units || b >= release_mark.load()) return;
         const int q = d.nq;
         hip_ok(hipEventRecord(d.t0[q], d.st), "hipEventRecord");
-        const int rc = gs_dsampler_run(d.ds, roots_dev + b * cfg.batch, cfg.batch, dpack[b % n_dpack], dcap, d.st);
+        // counter-based sampler: batch b under index b, whichever stream takes it
+        const int rc = fastmode ? gs_dsampler_run_at(d.ds, b, roots_dev + b * cfg.batch, cfg.batch, dpack[b % n_dpack],
+                                                     dcap, d.st)
+                                : gs_dsampler_run(d.ds, roots_dev + b * cfg.batch, cfg.batch, dpack[b % n_dpack], dcap,
+                                                  d.st);
         if (rc != GS_OK) fail(rc, gs_last_error());
         hip_ok(hipEventRecord(d.t1[q], d.st), "hipEventRecord");
         d.qb[q] = b;
@@ -428,6 +433,7 @@ void gs_runner::dev_poll() {
 // stream's run in flight).
 void gs_runner::dev_sync_rngs() {
     using namespace gs;
+    if (fastmode) return;
     for (int w = 0; w < static_cast<int>(dstreams.size()); ++w) {
         DevStream& d = dstreams[w];
         if (!d.ds) continue;
@@ -588,7 +594,10 @@ int gs_runner_create(const gs_runner_config* cfg, gs_runner** out) {
     GS_API_BEGIN
     using namespace gs;
     GS_REQUIRE(cfg && out, GS_EINVAL, "NULL argument");
-    GS_REQUIRE(cfg->graph && cfg->trainer && cfg->batches && cfg->rngs, GS_EINVAL, "NULL pointer in config");
+    const bool fast = cfg->device_sampler == 2;  // counter-based sampler: rngs ignored
+    GS_REQUIRE(cfg->graph && cfg->trainer && cfg->batches && (cfg->rngs || fast), GS_EINVAL,
+               "NULL pointer in config");
+    GS_REQUIRE(cfg->device_sampler >= 0 && cfg->device_sampler <= 2, GS_EINVAL, "device_sampler out of [0, 2]");
     GS_REQUIRE(cfg->n_batches >= 1 && cfg->batch >= 1 && cfg->batch < (int64_t(1) << 30), GS_EINVAL,
                "bad batch shape");
     GS_REQUIRE(cfg->n_hops >= 1 && cfg->n_hops <= GS_MAX_HOPS, GS_EINVAL, "n_hops out of [1, 8]");
@@ -599,7 +608,7 @@ int gs_runner_create(const gs_runner_config* cfg, gs_runner** out) {
                "embed_out needs embed_ld >= 1 and no communicator");
     GS_REQUIRE(cfg->merge <= 1 || cfg->embed_out, GS_EINVAL, "merge > 1 is inference only (embed_out)");
     GS_REQUIRE(cfg->helpers >= 0 && cfg->helpers <= 64, GS_EINVAL, "helpers out of [0, 64]");
-    for (int32_t w = 0; w < cfg->n_streams; ++w) GS_REQUIRE(cfg->rngs[w], GS_EINVAL, "NULL rng");
+    for (int32_t w = 0; w < cfg->n_streams && !fast; ++w) GS_REQUIRE(cfg->rngs[w], GS_EINVAL, "NULL rng");
     std::unique_ptr<gs_runner> r(new gs_runner());
     r->cfg = *cfg;
     r->fanouts.assign(cfg->fanouts ? cfg->fanouts : nullptr, cfg->fanouts ? cfg->fanouts + cfg->n_hops : nullptr);
@@ -673,6 +682,7 @@ int gs_runner_create(const gs_runner_config* cfg, gs_runner** out) {
     }
     const int32_t S = cfg->n_streams;
     r->devmode = cfg->device_sampler != 0;
+    r->fastmode = fast;
     if (r->devmode) {
         GS_REQUIRE(r->merge == 1, GS_EINVAL, "device_sampler: merge must be 1");
         GS_REQUIRE(!(cfg->flags & GS_SAMPLE_FULL), GS_EINVAL, "device_sampler: no GS_SAMPLE_FULL");
@@ -693,9 +703,15 @@ int gs_runner_create(const gs_runner_config* cfg, gs_runner** out) {
             }
             int rc = gs_dsampler_create(cfg->graph, r->fanouts.data(), cfg->n_hops, cfg->batch,
                                         (cfg->flags & (GS_SAMPLE_GCN | GS_SAMPLE_FAIL_EMPTY)) |
-                                            (S > 1 ? GS_DSAMPLER_NO_AUX : 0),
+                                            (fast ? GS_DSAMPLER_FAST : S > 1 ? GS_DSAMPLER_NO_AUX : 0),
                                         &d.ds);
             if (rc != GS_OK) fail(rc, gs_last_error());
+            d.next = w;
+            if (fast) {
+                rc = gs_dsampler_set_seed(d.ds, cfg->sampler_seed);
+                if (rc != GS_OK) fail(rc, gs_last_error());
+                continue;
+            }
             uint32_t mt[624];
             int64_t pos = 0;
             rc = gs_rng_get_state(cfg->rngs[w], mt, &pos);

@@ -267,10 +267,17 @@ class GraphSage(nn.Module):
                 draws, pack and `random` state as the host sampler (fanouts
                 1..32 before the last hop, <= 32 at it).  For large batches
                 (an apply_model forward over an extended batch).
+                "fast": the counter-based device sampler instead (DESIGN §5d,
+                sampler.FastDeviceSampler; fanouts 1..32): uniform sampling
+                from Philox words keyed by `sampler_seed`, no parity with the
+                reference's stream.  Each forward samples with batch index
+                `self.batch_index` and then increments it (set it to replay a
+                forward); the global `random` is neither read nor advanced.
     """
 
     def __init__(self, num_layers, input_size, out_size, raw_features, adj_lists, device, gcn=False,
-                 agg_func='MEAN', *, fanouts=None, rng=None, sampler_helpers=0, device_sampler=False):
+                 agg_func='MEAN', *, fanouts=None, rng=None, sampler_helpers=0, device_sampler=False,
+                 sampler_seed=0):
         super().__init__()
         self.input_size = input_size
         self.out_size = out_size
@@ -289,7 +296,15 @@ class GraphSage(nn.Module):
         self._pin = None        # pinned pack buffer of the team path
         self._pin_ev = None     # its last H2D copy
         self._graph = adj_lists if isinstance(adj_lists, CSRGraph) else None
-        self.device_sampler = bool(device_sampler)
+        self.fast_sampler = isinstance(device_sampler, str)
+        if self.fast_sampler:
+            if device_sampler != "fast":
+                raise ValueError("device_sampler must be True, False or 'fast'")
+            if any(k is None or not 1 <= int(k) <= 32 for k in self.fanouts):
+                raise ValueError("device_sampler='fast': fanouts must be in [1, 32]")
+        self.sampler_seed = int(sampler_seed)
+        self.batch_index = 0    # the next forward's batch index (fast sampler)
+        self.device_sampler = bool(device_sampler) and not self.fast_sampler
         if self.device_sampler:
             ks = self.fanouts
             if any(k is None or int(k) > 32 for k in ks) or any(int(k) < 1 for k in ks[:-1]):
@@ -404,6 +419,31 @@ class GraphSage(nn.Module):
         out._native = (hs, np.asarray(offs, np.int64).reshape(-1))
         return out
 
+    def _draw_fast(self, roots, device):
+        """The forward's sample from the counter-based device sampler: a pure
+        function of (sampler_seed, batch_index, roots); no random stream."""
+        from .sampler import FastDeviceSampler
+        n = len(roots)
+        dev = torch.device(device)
+        if self._dsampler is None or self._dsampler_cap < n or self._dsampler.device != dev:
+            cap = max(n, 512)
+            self._dsampler = FastDeviceSampler(self.graph, self.fanouts, cap, self.sampler_seed, gcn=self.gcn,
+                                               fail_empty=self.agg_func == "MAX", device=dev)
+            self._dsampler_cap = cap
+        self._dsampler.set_seed(self.sampler_seed)
+        index = self.batch_index
+        self.batch_index = index + 1
+        try:
+            pack, sizes, offs, used = self._dsampler.run(roots, index)
+        except IndexError:
+            raise IndexError("MAX aggregation over an empty neighbourhood (reference: models.py:321-325)")
+        L = len(self.fanouts)
+        hs = np.ascontiguousarray(np.asarray(sizes, np.int64).reshape(-1)[:4 * L])
+        offs = np.ascontiguousarray(np.asarray(offs, np.int64).reshape(-1))
+        out = DeviceSample(_PackInfo(L, hs, offs), device, buf=pack[:used])
+        out._native = (hs, offs)
+        return out
+
     @staticmethod
     def _roots(nodes_batch):
         if isinstance(nodes_batch, torch.Tensor):
@@ -423,7 +463,10 @@ class GraphSage(nn.Module):
         if self.agg_func not in ("MEAN", "MAX"):
             raise ValueError(f"agg_func must be 'MEAN' or 'MAX', got {self.agg_func!r}")
         # the device sampler returns None for a batch past its capacities
-        ds = self._draw_device(roots, X.device) if self.device_sampler else None
+        if self.fast_sampler:
+            ds = self._draw_fast(roots, X.device)
+        else:
+            ds = self._draw_device(roots, X.device) if self.device_sampler else None
         if ds is None and self.sampler_helpers > 0 and self.agg_func == "MEAN":
             ds = self._draw_pack(roots, X.device)
         elif ds is None:

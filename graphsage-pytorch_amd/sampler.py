@@ -8,6 +8,11 @@ interleaved with other ``random`` users such as UnsupervisedLoss).
 ``sample`` runs every hop of a forward; the result holds the host views
 (frontiers in CPython set order, sampled sets) and packs the int32 image the
 kernels read into one buffer for a single host->device copy.
+
+``fast_sample`` / ``FastDeviceSampler`` are the counter-based sampler (DESIGN
+§5d): uniform without-replacement sampling from Philox words, a pure function
+of (graph, seed, batch_index, roots), with no parity with the reference's
+``random`` stream; the same pack layout, so everything downstream is shared.
 """
 import array as _array
 import ctypes
@@ -209,6 +214,44 @@ def sample(graph, rng, roots, fanouts, gcn=False, full=False):
     return Sample(h.value)
 
 
+def _fanouts(fanouts):
+    if any(k is None for k in fanouts):
+        raise ValueError("the counter-based sampler needs a fanout in [1, 32] at every hop")
+    return np.ascontiguousarray([int(k) for k in fanouts], np.int32)
+
+
+def fast_sample(graph, seed, batch_index, roots, fanouts, gcn=False, fail_empty=False):
+    """One batch of the counter-based sampler on the host (gs_fsample_pack_run,
+    the CPU mirror of FastDeviceSampler): returns (pack int32 tensor,
+    hop_sizes[n_hops, 4], offsets[8, 8], used).  The roots (int32) sit at
+    pack[used - len(roots):used].  Reads and advances no random stream."""
+    roots = np.ascontiguousarray(np.asarray(roots).reshape(-1), dtype=np.int64)
+    fan = _fanouts(fanouts)
+    flags = (_lib.GS_SAMPLE_GCN if gcn else 0) | (_lib.GS_SAMPLE_FAIL_EMPTY if fail_empty else 0)
+    bound = int(lib().gs_sample_pack_bound(graph.handle, len(roots), ptr(fan), len(fan)))
+    if bound < 0:
+        raise ValueError("empty nodes_batch or bad fanouts")
+    pack = torch.zeros(bound + len(roots), dtype=torch.int32)
+    hs = np.zeros(4 * _lib.GS_MAX_HOPS, np.int64)
+    off = np.zeros(_lib.GS_MAX_HOPS * _lib.GS_PK_NFIELDS, np.int64)
+    used = ctypes.c_int64()
+    check(lib().gs_fsample_pack_run(graph.handle, int(seed) & (2 ** 64 - 1), int(batch_index), ptr(roots), len(roots),
+                                    ptr(fan), len(fan), flags, ptr(pack), int(pack.numel()), ptr(hs), ptr(off),
+                                    ctypes.byref(used)))
+    return pack, hs.reshape(-1, 4)[:len(fan)], off.reshape(_lib.GS_MAX_HOPS, _lib.GS_PK_NFIELDS), int(used.value)
+
+
+def philox4x32(ctr, key):
+    """One Philox4x32-10 block (known answers): 4 counter and 2 key words -> 4 words."""
+    ctr = np.ascontiguousarray(ctr, np.uint32)
+    key = np.ascontiguousarray(key, np.uint32)
+    if ctr.shape != (4,) or key.shape != (2,):
+        raise ValueError("philox4x32 takes 4 counter words and 2 key words")
+    out = np.zeros(4, np.uint32)
+    check(lib().gs_philox4x32(ptr(ctr), ptr(key), ptr(out)))
+    return out
+
+
 class DeviceSampler:
     """The hop loop of GraphSage.forward (models.py:246-251 over
     _get_unique_neighs_list, :277-289) on the GPU: a device
@@ -269,6 +312,69 @@ class DeviceSampler:
                   and pack.device == self.device):
             raise ValueError(f"pack must be a contiguous int32 tensor on {self.device}")
         check(lib().gs_dsampler_run(self._h, ptr(roots), n, ptr(pack), int(pack.numel()), _lib.stream_ptr(self.device)))
+        hs = np.zeros(4 * _lib.GS_MAX_HOPS, np.int64)
+        off = np.zeros(_lib.GS_MAX_HOPS * _lib.GS_PK_NFIELDS, np.int64)
+        used = ctypes.c_int64()
+        check(lib().gs_dsampler_result(self._h, ptr(hs), ptr(off), ctypes.byref(used)))
+        return pack, hs.reshape(-1, 4)[:self.n_hops], off.reshape(_lib.GS_MAX_HOPS, _lib.GS_PK_NFIELDS), \
+            int(used.value)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and getattr(_lib, "_lib", None) is not None:  # _lib is None at interpreter exit
+            _lib._lib.gs_dsampler_destroy(h)
+            self._h = None
+
+
+class FastDeviceSampler:
+    """The counter-based sampler on the GPU (a gs_dsampler created
+    with GS_DSAMPLER_FAST): ``run(roots, batch_index)`` writes, in device
+    memory, the pack ``fast_sample(graph, seed, batch_index, roots, ...)``
+    writes on the host — bit for bit.  Stateless between runs; no host threads
+    and no ``random`` stream."""
+
+    def __init__(self, graph, fanouts, max_roots, seed, gcn=False, fail_empty=False, device=None):
+        self.fanouts = _fanouts(fanouts)
+        flags = (_lib.GS_SAMPLE_GCN if gcn else 0) | (_lib.GS_SAMPLE_FAIL_EMPTY if fail_empty else 0)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("FastDeviceSampler runs on a HIP device")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            check(lib().gs_dsampler_create(graph._h, ptr(self.fanouts), len(self.fanouts), int(max_roots),
+                                           flags | _lib.GS_DSAMPLER_FAST, ctypes.byref(h)))
+        self._h = h
+        self.graph = graph  # keep the host graph alive (pack bounds)
+        self.n_hops = len(self.fanouts)
+        self.set_seed(seed)
+
+    def set_seed(self, seed):
+        self.seed = int(seed) & (2 ** 64 - 1)
+        check(lib().gs_dsampler_set_seed(self._h, self.seed))
+
+    def pack_bound(self, n_roots):
+        return int(lib().gs_dsampler_pack_bound(self._h, int(n_roots)))
+
+    def run(self, roots, batch_index, pack=None):
+        """Sample one batch; returns (pack, hop_sizes[n_hops, 4], offsets[8, 8], used)."""
+        if not isinstance(roots, torch.Tensor):
+            roots = torch.as_tensor(np.asarray(roots, np.int64).astype(np.int32))
+        # device pointers only: a CPU or strided roots tensor would hand the
+        # kernels host memory or the wrong ids
+        roots = roots.to(device=self.device, dtype=torch.int32).contiguous().view(-1)
+        n = int(roots.numel())
+        if pack is None:
+            bound = self.pack_bound(n)
+            if bound < 0:
+                raise ValueError("n_roots out of [1, max_roots]")
+            pack = torch.zeros(bound, dtype=torch.int32, device=self.device)
+        elif not (isinstance(pack, torch.Tensor) and pack.dtype == torch.int32 and pack.is_contiguous()
+                  and pack.device == self.device):
+            raise ValueError(f"pack must be a contiguous int32 tensor on {self.device}")
+        check(lib().gs_dsampler_run_at(self._h, int(batch_index), ptr(roots), n, ptr(pack), int(pack.numel()),
+                                       _lib.stream_ptr(self.device)))
         hs = np.zeros(4 * _lib.GS_MAX_HOPS, np.int64)
         off = np.zeros(_lib.GS_MAX_HOPS * _lib.GS_PK_NFIELDS, np.int64)
         used = ctypes.c_int64()

@@ -383,16 +383,25 @@ class Runner:
     gs_dsampler: one per stream, each on its own HIP stream), writing every
     pack straight into the device ring — no host sampler threads; the same
     packs and stream consumption as the host sampler.  The rngs are updated
-    at ``sync_rngs()`` and ``close()``."""
+    at ``sync_rngs()`` and ``close()``.
+    `sampler="device-fast"`: the counter-based sampler on the GPU (DESIGN §5d,
+    sampler.FastDeviceSampler) under `seed`: batch b is sampled with
+    batch_index = b, so the packs depend on neither the stream count nor any
+    ``random`` stream.  `rngs` only gives the number of device streams (an
+    int, or a sequence whose items are ignored and left untouched)."""
 
     def __init__(self, trainer, graph, batches, rngs, fanouts, gcn=False, fail_empty=False, depth=4,
                  comm=None, embed_out=None, merge=1, hold=False, ar_buckets=1, helpers=0, warm=False,
-                 sampler="host"):
-        if sampler not in ("host", "device"):
-            raise ValueError("sampler must be 'host' or 'device'")
+                 sampler="host", seed=0):
+        if sampler not in ("host", "device", "device-fast"):
+            raise ValueError("sampler must be 'host', 'device' or 'device-fast'")
         self.sampler = sampler
         self.trainer, self.graph = trainer, graph
         self.embed_out = embed_out
+        fast = sampler == "device-fast"
+        if fast:
+            n_streams = int(rngs) if isinstance(rngs, int) else len(list(rngs))
+            rngs = []
         self.rngs = list(rngs)
         self.batches = np.ascontiguousarray(np.stack([np.asarray(b, np.int64) for b in batches]))
         self.fanouts = np.ascontiguousarray(fanouts, dtype=np.int32)
@@ -402,11 +411,11 @@ class Runner:
         cfg = _lib.RunnerConfig(
             graph=graph._h.value, trainer=trainer._h.value, batches=self.batches.ctypes.data,
             n_batches=self.batches.shape[0], batch=self.batches.shape[1], fanouts=self.fanouts.ctypes.data,
-            n_hops=len(self.fanouts), flags=flags, n_streams=len(self.rngs),
-            rngs=ctypes.cast(self._rng_ptrs, ctypes.c_void_p), depth=depth,
+            n_hops=len(self.fanouts), flags=flags, n_streams=n_streams if fast else len(self.rngs),
+            rngs=None if fast else ctypes.cast(self._rng_ptrs, ctypes.c_void_p), depth=depth,
             comm=comm._h.value if comm is not None else None, world=comm.world if comm is not None else 1,
             hold=int(bool(hold)), ar_buckets=int(ar_buckets), helpers=int(helpers), warm=int(bool(warm)),
-            device_sampler=int(sampler == "device"))
+            device_sampler=2 if fast else int(sampler == "device"), sampler_seed=int(seed) & (2 ** 64 - 1))
         if embed_out is not None:
             n_rows = self.batches.shape[0] * self.batches.shape[1]
             if not (embed_out.is_contiguous() and embed_out.dtype == torch.float32
@@ -482,7 +491,14 @@ class Embedder:
     one stream that is exactly the reference's sequence of GraphSage calls on
     one `random` stream, for any m."""
 
-    def __init__(self, graph, features, weights, fanouts, agg_func="MEAN", gcn=False, depth=4, merge=2, helpers=0):
+    def __init__(self, graph, features, weights, fanouts, agg_func="MEAN", gcn=False, depth=4, merge=2, helpers=0,
+                 sampler="host", seed=0):
+        if sampler not in ("host", "device-fast"):
+            raise ValueError("Embedder: sampler must be 'host' or 'device-fast'")
+        # "device-fast": the counter-based device sampler under `seed` (DESIGN
+        # §5d), one batch per launch; batch i of an embed() call is sampled
+        # with batch_index = i (the trailing partial batch included)
+        self.sampler, self.seed = sampler, int(seed)
         weights = [w.detach() for w in weights]
         H = weights[0].shape[0]
         dev = features.device
@@ -499,20 +515,32 @@ class Embedder:
     def embed(self, nodes, batch, rngs):
         """[len(nodes), hidden] fp32 embeddings on the device, row i = nodes[i]."""
         nodes = np.ascontiguousarray(nodes, dtype=np.int64).reshape(-1)
-        rngs = list(rngs)
+        rngs = [None] * rngs if isinstance(rngs, int) else list(rngs)
         n_full = len(nodes) // batch
         out = torch.empty(len(nodes), self.trainer.H, dtype=torch.float32, device=self.trainer.device)
+        fast = self.sampler == "device-fast"
+        merge = 1 if fast else self.merge
         if n_full:
-            r = Runner(self.trainer, self.graph, nodes[:n_full * batch].reshape(n_full, batch), rngs, self.fanouts,
+            r = Runner(self.trainer, self.graph, nodes[:n_full * batch].reshape(n_full, batch),
+                       len(rngs) if fast else rngs, self.fanouts,
                        gcn=self.gcn, fail_empty=self.agg == "MAX", depth=self.depth, embed_out=out,
-                       merge=self.merge, helpers=self.helpers)
+                       merge=merge, helpers=self.helpers, sampler=self.sampler, seed=self.seed)
             try:
-                r.run(-(-n_full // self.merge))
+                r.run(-(-n_full // merge))
                 self.last_stats = r.stats()
             finally:
                 r.close()  # joins the sampler threads: every rng has advanced past its batches
         rest = nodes[n_full * batch:]
-        if len(rest):
+        if len(rest) and fast:
+            from .sampler import FastDeviceSampler
+            fds = FastDeviceSampler(self.graph, self.fanouts, len(rest), self.seed, gcn=self.gcn,
+                                    fail_empty=self.agg == "MAX", device=self.trainer.device)
+            pack, hs, offs, used = fds.run(rest, n_full)
+            L = len(self.fanouts)
+            info = SampleInfo(L, hs.reshape(-1), offs, used, len(rest))
+            ds = DeviceSample(info, self.trainer.device, buf=pack[:used])
+            self.trainer.forward(ds, out[n_full * batch:])
+        elif len(rest):
             s = sample(self.graph, rngs[(n_full // self.merge) % len(rngs)], rest, self.fanouts, gcn=self.gcn)
             if self.agg == "MAX" and any(s.n_empty(j) for j in range(1, s.n_hops + 1)):
                 raise IndexError("MAX aggregation over an empty neighbourhood (reference: models.py:321-325)")

@@ -210,6 +210,24 @@ int gs_sample_pack_run_multi(const gs_graph* g, gs_rng* rng, const int64_t* root
                              int64_t n_roots, int64_t group, const int32_t* fanouts,
                              int32_t n_hops, int32_t flags, int32_t* buf, int64_t cap,
                              int64_t* hop_sizes, int64_t* offsets, int64_t* used);
+/* ------------------------------------------- counter-based (Philox) sampler
+ * Uniform without-replacement neighbour sampling that does not reproduce the
+ * reference's `random` stream (not a reference interface): a pack
+ * is a pure function of (graph, seed, batch_index, roots, fanouts, flags),
+ * with no sampler state.  Random words are Philox4x32-10 outputs, key =
+ * (seed low, seed high), counter = (slot r of the destination in F(j-1),
+ * j << 24 | t / 4, batch_index low, high) for draw t of 1-based hop j, word
+ * t % 4; a row longer than the fanout k (1..32) is sampled with Floyd's
+ * algorithm, a shorter one is taken whole; each frontier is in ascending node
+ * id order.  Layout, sizes, roots placement, bound (gs_sample_pack_bound) and
+ * GS_SAMPLE_GCN / GS_SAMPLE_FAIL_EMPTY are those of gs_sample_pack_run. */
+int gs_fsample_pack_run(const gs_graph* g, uint64_t seed, int64_t batch_index,
+                        const int64_t* roots, int64_t n_roots, const int32_t* fanouts,
+                        int32_t n_hops, int32_t flags, int32_t* buf, int64_t cap,
+                        int64_t* hop_sizes, int64_t* offsets, int64_t* used);
+/* Known answers: one Philox4x32-10 block, ctr[4], key[2] -> out[4]. */
+int gs_philox4x32(const uint32_t* ctr, const uint32_t* key, uint32_t* out);
+
 /* Helper threads for one sampling stream (not a reference interface: they
  * split the RNG-independent parts of a batch — the per-node set builds of
  * models.py:282-285 and the neighbour / transposed lists a hop's aggregate
@@ -245,6 +263,13 @@ typedef struct gs_dsampler gs_dsampler;
  * fork, one join per run) — it pays for one sampler alone on the GPU, not for
  * several sharing it (the runner sets this flag for S > 1). */
 #define GS_DSAMPLER_NO_AUX 8
+/* gs_dsampler_create flag: the handle is a counter-based sampler,
+ * the device form of gs_fsample_pack_run — same pack, bit for bit.  It holds
+ * no MT19937 stream: gs_dsampler_set_rng / get_rng / words / run / debug
+ * return GS_EINVAL; batches are sampled with gs_dsampler_run_at under the seed
+ * of gs_dsampler_set_seed (0 at create).  pack_bound, result, result_of and
+ * runs work as for the bit-exact handle.  Fanouts 1..32 at every hop. */
+#define GS_DSAMPLER_FAST 16
 int gs_dsampler_create(const gs_graph* g, const int32_t* fanouts, int32_t n_hops,
                        int64_t max_roots, int32_t flags, gs_dsampler** out);
 void gs_dsampler_destroy(gs_dsampler* ds);
@@ -262,6 +287,12 @@ int64_t gs_dsampler_pack_bound(const gs_dsampler* ds, int64_t n_roots);
 int gs_dsampler_run(gs_dsampler* ds, const int32_t* roots, int64_t n_roots, int32_t* pack,
                     int64_t cap, void* stream);
 int gs_dsampler_result(gs_dsampler* ds, int64_t* hop_sizes, int64_t* offsets, int64_t* used);
+/* GS_DSAMPLER_FAST handles: the seed of the following runs, and one batch
+ * sampled as gs_fsample_pack_run(g, seed, batch_index, ...) would sample it,
+ * asynchronously on `stream` (no state carries from run to run). */
+int gs_dsampler_set_seed(gs_dsampler* ds, uint64_t seed);
+int gs_dsampler_run_at(gs_dsampler* ds, int64_t batch_index, const int32_t* roots, int64_t n_roots,
+                       int32_t* pack, int64_t cap, void* stream);
 /* Runs issued so far on this sampler; run i (0-based) is gs_dsampler_run's
  * i-th call.  gs_dsampler_result_of(ds, i, ...) reports run i's layout (waits
  * for that run only), so a caller may keep a second run queued behind the one
@@ -691,6 +722,11 @@ typedef struct {
      * device runs the steps before it.  The rngs are written back at
      * gs_runner_sync_rngs and gs_runner_destroy. */
     int32_t device_sampler;
+    /* device_sampler == 2: the counter-based sampler (GS_DSAMPLER_FAST) under
+     * this seed; batch b is sampled with batch_index = b on whichever stream
+     * it lands, so the packs do not depend on n_streams.  rngs is ignored
+     * (may be NULL) and left untouched; gs_runner_sync_rngs is a no-op. */
+    uint64_t sampler_seed;
 } gs_runner_config;
 
 typedef struct {
@@ -724,7 +760,7 @@ int gs_runner_progress(const gs_runner* r, int64_t* sampled, int64_t* consumed);
 /* device_sampler runners: copy every device stream's state back into its
  * rngs[w] (waits for the stream's sampling in flight; the state then
  * includes every batch sampled so far, consumed or not — as the host
- * sampler threads' rngs do).  Host-sampler runners: no-op. */
+ * sampler threads' rngs do).  Host-sampler and counter-based runners: no-op. */
 int gs_runner_sync_rngs(gs_runner* r);
 void gs_runner_destroy(gs_runner* r);
 
