@@ -30,6 +30,7 @@ GS_DSAMPLER_FAST = 16   # gs_dsampler_create: the counter-based (Philox) sampler
 GS_SAMPLE_FAIL_EMPTY = 4
 GS_MAX_HOPS = 8
 GS_TOPT_FUSED_BWD, GS_TOPT_TOP_LAUNCH, GS_TOPT_SELF_ROWS, GS_TOPT_DEFER_UPDATE, GS_TOPT_TOP_PAIR = range(5)
+GS_OPT_SGD, GS_OPT_ADAM = 0, 1
 (GS_PK_POS_PTR, GS_PK_POS, GS_PK_DST_IDS, GS_PK_NBR_PTR, GS_PK_NBR, GS_PK_SELF,
  GS_PK_TPTR, GS_PK_TIDX, GS_PK_NFIELDS) = range(9)
 
@@ -115,6 +116,8 @@ _SIGS = {
     "gs_cls_nll_fwd_bwd": (_i32, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
                                   _vp, _vp, _vp]),
     "gs_clip_sgd": (_i32, [_i32, _vp, _vp, _vp, _f32, _f32, _f32, _vp, _vp]),
+    "gs_clip_adam": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i64, _vp,
+                            _vp]),
     "gs_unsup_create": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _p(_vp)]),
     "gs_unsup_destroy": (None, [_vp]),
     "gs_unsup_attach_device": (_i32, [_vp, _vp]),
@@ -149,6 +152,8 @@ _SIGS = {
     "gs_trainer_kernel_name": (ctypes.c_char_p, [_vp, _i32]),
     "gs_trainer_grads": (_vp, [_vp]),
     "gs_trainer_set_option": (_i32, [_vp, _i32, _i32]),
+    "gs_trainer_set_optimizer": (_i32, [_vp, _vp]),
+    "gs_trainer_opt_step": (_i64, [_vp]),
     "gs_trainer_capture": (_i32, [_vp, _vp, _i64, _vp, _i64]),
     "gs_trainer_captured": (_i64, [_vp]),
     "gs_comm_unique_id": (_i32, [_vp]),
@@ -185,6 +190,13 @@ class TrainerConfig(ctypes.Structure):
         ("feat_dtype", _i32), ("feat_dim", _i64), ("feat_ld", _i64),
         ("X", _vp), ("row_ptr", _vp), ("col", _vp), ("labels", _vp), ("params", _vp), ("grads", _vp),
         ("lr", _f32), ("max_norm", _f32),
+    ]
+
+
+class OptimizerConfig(ctypes.Structure):
+    _fields_ = [
+        ("kind", _i32), ("beta1", _f32), ("beta2", _f32), ("eps", _f32), ("weight_decay", _f32),
+        ("m", _vp), ("v", _vp), ("step", _i64),
     ]
 
 

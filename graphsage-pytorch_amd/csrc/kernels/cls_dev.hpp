@@ -123,6 +123,35 @@ __device__ __forceinline__ float sgd_elem(float p, float g, float m, float lr, f
     return fmaf(-lr, gi, p);
 }
 
+// One Adam / AdamW update's launch constants, computed on the host in double
+// from the step number t >= 1 (adam_hyper, misc.hip): no step counter on the
+// device.
+struct AdamHyper {
+    float b1, omb1;      // β1, 1 - β1
+    float b2, omb2;      // β2, 1 - β2
+    float eps;
+    float step_size;     // lr / (1 - β1^t)
+    float inv_sqrt_bc2;  // 1 / sqrt(1 - β2^t)
+    float decay;         // 1 - lr·weight_decay (exactly 1: no decay)
+};
+
+// One parameter's clip + AdamW step (torch.optim.AdamW's arithmetic): the
+// clipped gradient to gi, the moments updated in place, the new value
+// returned.  The scalar and the float4 kernel both go through here, and
+// every fused multiply-add is written out with contraction off, so the two
+// agree bit for bit.  p · decay with decay == 1 is p: weight_decay = 0 skips
+// the decay without a branch.
+__device__ __forceinline__ float adam_elem(float p, float g, float mult, const AdamHyper& h, float& gi, float& m,
+                                           float& v) {
+#pragma clang fp contract(off)
+    gi = g * mult;
+    const float pd = p * h.decay;
+    m = fmaf(h.omb1, gi, h.b1 * m);
+    v = fmaf(h.omb2, gi * gi, h.b2 * v);
+    const float denom = fmaf(sqrtf(v), h.inv_sqrt_bc2, h.eps);
+    return fmaf(-h.step_size, m / denom, pd);
+}
+
 // Clip (per group, utils.py:186-187) + SGD (utils.py:187-190) on float4
 // (every group offset a multiple of 4, 16-B aligned arrays), block bx of
 // nblk: wave w folds group w's norm partials (lane-strided loads, then a

@@ -119,6 +119,25 @@ void sgd_with_parts(int32_t n_groups, const int64_t* goff_host, const int* npart
 // gs_clip_sgd (the norm launch, then the SGD)
 void clip_sgd_launch(int32_t n_groups, const int64_t* goff_host, float* params, float* grads, float grad_scale,
                      float max_norm, float lr, float* ws, hipStream_t st, LowpShadow shadow = {}, DoneFlag done = {});
+// One Adam / AdamW update as its launchers take it: the hyper-parameters and
+// the number t >= 1 of the update being applied (the bias corrections are
+// computed on the host from it and passed to the kernel).
+struct AdamStep {
+    float lr, beta1, beta2, eps, weight_decay;
+    int64_t step;
+};
+// GS_EINVAL unless both betas are in [0, 1), eps > 0 and weight_decay >= 0.
+void adam_require(float beta1, float beta2, float eps, float weight_decay);
+// The clip + Adam launches, mirroring the two SGD forms (m, v: the moments,
+// as long as params; shadow and done as above).  Every argument is checked
+// before the first HIP call.
+void adam_with_parts(int32_t n_groups, const int64_t* goff_host, const int* npart, int pstride, float* params,
+                     float* grads, float* m, float* v, const float* part, float grad_scale, float max_norm,
+                     const AdamStep& a, hipStream_t st, LowpShadow shadow = {}, DoneFlag done = {});
+// gs_clip_adam (the norm launch, then the Adam update)
+void clip_adam_launch(int32_t n_groups, const int64_t* goff_host, float* params, float* grads, float* m, float* v,
+                      float grad_scale, float max_norm, const AdamStep& a, float* ws, hipStream_t st,
+                      LowpShadow shadow = {}, DoneFlag done = {});
 // The deferred update after an all-reduce: gs_clip_sgd's norm partials (into
 // part, kNormBlocks per group; returns that count) and W1's speculative update
 // S = P - lr·(scale·g) (+ S_lp in bf16) for the elements [0, n1); stores the

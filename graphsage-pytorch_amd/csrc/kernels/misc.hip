@@ -353,6 +353,92 @@ __global__ __launch_bounds__(kTb) void sgd4_kernel(Groups G, float* __restrict__
     sgd4_body(G, p, g, part, scale, max_norm, lr, blockIdx.x, gridDim.x);
 }
 
+// ------------------------------------------------------- clip + Adam / AdamW
+// sgd_kernel's clip (the same fold of the partials, in the same order, in
+// every block), then adam_elem per element: g is left clipped, m / v / p
+// updated, the new params of [sh_lo, sh_hi) also go to the bf16 shadow.
+__global__ __launch_bounds__(kTb) void adam_kernel(Groups G, float* __restrict__ p, float* __restrict__ g,
+                                                   float* __restrict__ m, float* __restrict__ v,
+                                                   const float* __restrict__ part, float scale, float max_norm,
+                                                   AdamHyper h, int64_t* done, int64_t done_value) {
+    signal_done(done, done_value);
+    __shared__ float mult[8];
+    const int lane = threadIdx.x & 63;
+    for (int grp = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); grp < G.n; grp += kTb / 64) {
+        const float t = clip_fold(part + grp * G.pstride, G.npart[grp], lane);
+        if (lane == 0) mult[grp] = clip_mult(t, scale, max_norm);
+    }
+    __syncthreads();
+    const int64_t total = G.off[G.n];
+    for (int64_t i = blockIdx.x * int64_t(kTb) + threadIdx.x; i < total; i += int64_t(gridDim.x) * kTb) {
+        int grp = 0;
+        while (i >= G.off[grp + 1]) ++grp;
+        float gi, mi = m[i], vi = v[i];
+        const float pn = adam_elem(p[i], g[i], mult[grp], h, gi, mi, vi);
+        g[i] = gi;
+        m[i] = mi;
+        v[i] = vi;
+        p[i] = pn;
+        if (G.sh && i >= G.sh_lo && i < G.sh_hi) G.sh[i - G.sh_lo] = f2bf(pn);
+    }
+}
+
+// adam_kernel on float4 (every group offset a multiple of 4, 16-B aligned
+// arrays): each thread's first g / p / m / v quads are loaded before the
+// fold, as in sgd4_body, so the two dependent rounds overlap.
+__global__ __launch_bounds__(kTb) void adam4_kernel(Groups G, float* __restrict__ p, float* __restrict__ g,
+                                                    float* __restrict__ m, float* __restrict__ v,
+                                                    const float* __restrict__ part, float scale, float max_norm,
+                                                    AdamHyper h, int64_t* done, int64_t done_value) {
+    signal_done(done, done_value);
+    __shared__ float mult[8];
+    const int64_t n4 = G.off[G.n] / 4;
+    const int64_t i0 = blockIdx.x * int64_t(kTb) + threadIdx.x;
+    float4* g4 = reinterpret_cast<float4*>(g);
+    float4* p4 = reinterpret_cast<float4*>(p);
+    float4* m4 = reinterpret_cast<float4*>(m);
+    float4* v4 = reinterpret_cast<float4*>(v);
+    float4 gv = make_float4(0.f, 0.f, 0.f, 0.f), pv = gv, mv = gv, vv = gv;
+    if (i0 < n4) {
+        gv = g4[i0];
+        pv = p4[i0];
+        mv = m4[i0];
+        vv = v4[i0];
+    }
+    const int lane = threadIdx.x & 63;
+    for (int grp = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); grp < G.n; grp += kTb / 64) {
+        const float t = clip_fold(part + grp * G.pstride, G.npart[grp], lane);
+        if (lane == 0) mult[grp] = clip_mult(t, scale, max_norm);
+    }
+    __syncthreads();
+    for (int64_t i = i0; i < n4; i += int64_t(gridDim.x) * kTb) {
+        if (i != i0) {
+            gv = g4[i];
+            pv = p4[i];
+            mv = m4[i];
+            vv = v4[i];
+        }
+        int grp = 0;
+        while (4 * i >= G.off[grp + 1]) ++grp;
+        const float mu = mult[grp];
+        float4 gi, pn;
+        pn.x = adam_elem(pv.x, gv.x, mu, h, gi.x, mv.x, vv.x);
+        pn.y = adam_elem(pv.y, gv.y, mu, h, gi.y, mv.y, vv.y);
+        pn.z = adam_elem(pv.z, gv.z, mu, h, gi.z, mv.z, vv.z);
+        pn.w = adam_elem(pv.w, gv.w, mu, h, gi.w, mv.w, vv.w);
+        g4[i] = gi;
+        m4[i] = mv;
+        v4[i] = vv;
+        p4[i] = pn;
+        if (G.sh && 4 * i >= G.sh_lo && 4 * i < G.sh_hi) {  // sh_lo, sh_hi multiples of 4
+            uint2 b;
+            b.x = static_cast<uint32_t>(f2bf(pn.x)) | (static_cast<uint32_t>(f2bf(pn.y)) << 16);
+            b.y = static_cast<uint32_t>(f2bf(pn.z)) | (static_cast<uint32_t>(f2bf(pn.w)) << 16);
+            *reinterpret_cast<uint2*>(G.sh + (4 * i - G.sh_lo)) = b;
+        }
+    }
+}
+
 }  // namespace gs
 
 extern "C" {
@@ -469,6 +555,88 @@ void clip_sgd_launch(int32_t n_groups, const int64_t* goff_host, float* params, 
     check_launch("gs_clip_sgd");
 }
 
+void adam_require(float beta1, float beta2, float eps, float weight_decay) {
+    GS_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, GS_EINVAL, "betas must be in [0, 1)");
+    GS_REQUIRE(eps > 0.f, GS_EINVAL, "eps must be positive");
+    GS_REQUIRE(weight_decay >= 0.f, GS_EINVAL, "weight_decay must not be negative");
+}
+
+// The launch constants of update a.step (the bias corrections in double).
+static AdamHyper adam_hyper(const AdamStep& a) {
+    adam_require(a.beta1, a.beta2, a.eps, a.weight_decay);
+    GS_REQUIRE(a.step >= 1, GS_EINVAL, "step must be >= 1 (the update being applied)");
+    const double b1 = a.beta1, b2 = a.beta2, t = static_cast<double>(a.step);
+    AdamHyper h;
+    h.b1 = a.beta1;
+    h.omb1 = static_cast<float>(1.0 - b1);
+    h.b2 = a.beta2;
+    h.omb2 = static_cast<float>(1.0 - b2);
+    h.eps = a.eps;
+    h.step_size = static_cast<float>(static_cast<double>(a.lr) / (1.0 - std::pow(b1, t)));
+    h.inv_sqrt_bc2 = static_cast<float>(1.0 / std::sqrt(1.0 - std::pow(b2, t)));
+    h.decay = static_cast<float>(1.0 - static_cast<double>(a.lr) * static_cast<double>(a.weight_decay));
+    return h;
+}
+
+// The Adam launch over filled-in groups: float4 under sgd_with_parts' rule
+// (16-byte aligned arrays, every group offset and the shadow range a
+// multiple of 4), else the scalar kernel.
+static void adam_launch(Groups& G, float* params, float* grads, float* m, float* v, const float* part,
+                        float grad_scale, float max_norm, const AdamHyper& h, hipStream_t st, LowpShadow sh,
+                        DoneFlag done) {
+    G.sh = sh.p;
+    G.sh_lo = sh.lo;
+    G.sh_hi = sh.hi;
+    const int64_t total = G.off[G.n];
+    bool vec = aligned16(params) && aligned16(grads) && aligned16(m) && aligned16(v);
+    for (int i = 0; i <= G.n; ++i) vec = vec && G.off[i] % 4 == 0;
+    vec = vec && (!sh.p || (sh.lo % 4 == 0 && sh.hi % 4 == 0 && reinterpret_cast<uintptr_t>(sh.p) % 8 == 0));
+    const int64_t n = vec ? total / 4 : total;
+    const dim3 grid(static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>((n + kTb - 1) / kTb, 512))));
+    if (vec)
+        adam4_kernel<<<grid, kTb, 0, st>>>(G, params, grads, m, v, part, grad_scale, max_norm, h, done.ptr,
+                                           done.value);
+    else
+        adam_kernel<<<grid, kTb, 0, st>>>(G, params, grads, m, v, part, grad_scale, max_norm, h, done.ptr,
+                                          done.value);
+    check_launch("adam");
+}
+
+// Every argument check of the two Adam launch forms (before any HIP call).
+static void adam_groups(Groups& G, int32_t n_groups, const int64_t* goff_host, const float* params,
+                        const float* grads, const float* m, const float* v, const float* part) {
+    GS_REQUIRE(n_groups >= 1 && n_groups <= 8, GS_EINVAL, "1..8 parameter groups");
+    GS_REQUIRE(goff_host && params && grads && m && v && part, GS_EINVAL, "NULL pointer");
+    G.n = n_groups;
+    for (int i = 0; i <= n_groups; ++i) G.off[i] = goff_host[i];
+    GS_REQUIRE(G.off[0] >= 0, GS_EINVAL, "negative group offset");
+    for (int i = 0; i < n_groups; ++i) GS_REQUIRE(G.off[i] <= G.off[i + 1], GS_EINVAL, "group offsets not sorted");
+}
+
+void adam_with_parts(int32_t n_groups, const int64_t* goff_host, const int* npart, int pstride, float* params,
+                     float* grads, float* m, float* v, const float* part, float grad_scale, float max_norm,
+                     const AdamStep& a, hipStream_t st, LowpShadow sh, DoneFlag done) {
+    Groups G;
+    adam_groups(G, n_groups, goff_host, params, grads, m, v, part);
+    GS_REQUIRE(npart, GS_EINVAL, "NULL pointer");
+    const AdamHyper h = adam_hyper(a);
+    G.pstride = pstride;
+    for (int i = 0; i < n_groups; ++i) G.npart[i] = npart[i];
+    adam_launch(G, params, grads, m, v, part, grad_scale, max_norm, h, st, sh, done);
+}
+
+void clip_adam_launch(int32_t n_groups, const int64_t* goff_host, float* params, float* grads, float* m, float* v,
+                      float grad_scale, float max_norm, const AdamStep& a, float* ws, hipStream_t st, LowpShadow sh,
+                      DoneFlag done) {
+    Groups G;
+    adam_groups(G, n_groups, goff_host, params, grads, m, v, ws);
+    const AdamHyper h = adam_hyper(a);
+    G.pstride = kNormBlocks;
+    for (int i = 0; i < n_groups; ++i) G.npart[i] = kNormBlocks;
+    group_sumsq_kernel<<<dim3(kNormBlocks, n_groups), kTb, 0, st>>>(G, grads, ws);
+    adam_launch(G, params, grads, m, v, ws, grad_scale, max_norm, h, st, sh, done);
+}
+
 }  // namespace gs
 
 extern "C" {
@@ -493,6 +661,15 @@ int gs_clip_sgd(int32_t n_groups, const int64_t* goff_host, float* params, float
                 float max_norm, float lr, float* ws, void* stream) {
     GS_API_BEGIN
     gs::clip_sgd_launch(n_groups, goff_host, params, grads, grad_scale, max_norm, lr, ws, gs::as_stream(stream));
+    GS_API_END
+}
+
+int gs_clip_adam(int32_t n_groups, const int64_t* goff_host, float* params, float* grads, float* m, float* v,
+                 float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay,
+                 int64_t step, float* ws, void* stream) {
+    GS_API_BEGIN
+    gs::clip_adam_launch(n_groups, goff_host, params, grads, m, v, grad_scale, max_norm,
+                         gs::AdamStep{lr, beta1, beta2, eps, weight_decay, step}, ws, gs::as_stream(stream));
     GS_API_END
 }
 

@@ -128,6 +128,11 @@ struct gs_trainer {
         int64_t max_steps = 0, n = 0;
     } cap;
     const float* last_emb = nullptr;  // the last run_step's [B, H] top-layer output
+    // The optimiser of gs_trainer_update[_local] (gs_trainer_set_optimizer):
+    // clip + SGD, or clip + Adam on the caller's moment buffers, opt.step
+    // counting the updates applied to them.  Adam never defers (the deferred
+    // update's speculation is sgd_elem): every update is a launch of its own.
+    gs_optimizer_config opt{GS_OPT_SGD, 0.9f, 0.999f, 1e-8f, 0.f, nullptr, nullptr, 0};
     // the runner's step-completion flag (trainer_set_done), until the launch that stores it is issued
     gs::DoneFlag done;
     gs::DoneFlag take_done() {
@@ -742,6 +747,22 @@ static void w1_home(gs_trainer* t, hipStream_t st) {
     t->w1_cur = 0;
 }
 
+// The trainer's clip + Adam update number opt.step + 1: one launch from the
+// step's own norm partials (parts), else the norm launch into ws first.
+static void adam_update(gs_trainer* t, bool parts, float grad_scale, float* ws, hipStream_t st, LowpShadow shadow) {
+    const gs_trainer_config& c = t->cfg;
+    const gs_optimizer_config& o = t->opt;
+    const int64_t goff[3] = {0, t->cls_w_off, t->total};
+    const AdamStep a{c.lr, o.beta1, o.beta2, o.eps, o.weight_decay, o.step + 1};
+    if (parts)
+        adam_with_parts(2, goff, t->npart, t->pstride, c.params, c.grads, o.m, o.v, t->norm_part, grad_scale,
+                        c.max_norm, a, st, shadow, t->take_done());
+    else
+        clip_adam_launch(2, goff, c.params, c.grads, o.m, o.v, grad_scale, c.max_norm, a, ws, st, shadow,
+                         t->take_done());
+    ++t->opt.step;
+}
+
 bool trainer_defer_update(gs_trainer* t, bool on, hipStream_t st, bool comm) {
     if (!on) {
         if (t->pending) {  // the last step's clip + SGD: the flat params become what sgd4 would leave
@@ -762,7 +783,9 @@ bool trainer_defer_update(gs_trainer* t, bool on, hipStream_t st, bool comm) {
     // its feature rows must take 16-B loads (run_step re-checks each step's
     // operands and applies the update on its own where they do not)
     const int64_t epv = c.feat_dtype == GS_F32 ? 4 : 8;
-    const bool ok = t->opt_defer && (c.feat_dtype == GS_F32 || (c.feat_dtype == GS_BF16 && t->w1_lp)) &&
+    // (and only SGD is speculated on: sgd_elem in the slab sum, FwdSpec, sumsq_spec, spec_finalize)
+    const bool ok = t->opt.kind == GS_OPT_SGD && t->opt_defer &&
+                    (c.feat_dtype == GS_F32 || (c.feat_dtype == GS_BF16 && t->w1_lp)) &&
                     t->fuse_bwd && t->use_top && c.n_layers == 2 && !c.gcn &&
                     (comm || (!t->upper_hook && !t->w1_chunk_hook)) && n1 % 4 == 0 &&
                     c.feat_dim % epv == 0 && c.feat_ld % epv == 0 && aligned16(c.X) &&
@@ -847,6 +870,23 @@ int gs_trainer_set_option(gs_trainer* t, int32_t opt, int32_t value) {
     }
     GS_API_END
 }
+
+int gs_trainer_set_optimizer(gs_trainer* t, const gs_optimizer_config* oc) {
+    GS_API_BEGIN
+    GS_REQUIRE(t && oc, GS_EINVAL, "NULL argument");
+    GS_REQUIRE(oc->kind == GS_OPT_SGD || oc->kind == GS_OPT_ADAM, GS_EINVAL, "unknown optimizer kind");
+    GS_REQUIRE(!t->defer && !t->pending && !t->lp_keep, GS_EINVAL,
+               "the optimizer cannot change while deferring, with an update pending or inside a runner loop");
+    if (oc->kind == GS_OPT_ADAM) {
+        gs::adam_require(oc->beta1, oc->beta2, oc->eps, oc->weight_decay);
+        GS_REQUIRE(oc->m && oc->v, GS_EINVAL, "NULL moment buffer");
+        GS_REQUIRE(oc->step >= 0, GS_EINVAL, "negative step count");
+    }
+    t->opt = *oc;
+    GS_API_END
+}
+
+int64_t gs_trainer_opt_step(const gs_trainer* t) { return t ? t->opt.step : -1; }
 
 int64_t gs_trainer_ws_bytes(gs_trainer* t, const int64_t* hop_sizes) {
     try {
@@ -1111,7 +1151,9 @@ int gs_trainer_update_local(gs_trainer* t, void* stream) {
     const int64_t goff[3] = {0, t->cls_w_off, t->total};
     t->lp_valid = false;
     const gs::LowpShadow shadow = gs::lowp_shadow(t);
-    if (t->norm_ready) {
+    if (t->opt.kind == GS_OPT_ADAM) {
+        gs::adam_update(t, t->norm_ready, 1.0f, t->norm_part, gs::as_stream(stream), shadow);
+    } else if (t->norm_ready) {
         gs::sgd_with_parts(2, goff, t->npart, t->pstride, t->cfg.params, t->cfg.grads, t->norm_part, 1.0f,
                            t->cfg.max_norm, t->cfg.lr, gs::as_stream(stream), shadow, t->take_done());
     } else {
@@ -1150,8 +1192,11 @@ int gs_trainer_update(gs_trainer* t, float grad_scale, float* ws, void* stream) 
     const int64_t goff[3] = {0, t->cls_w_off, t->total};
     t->lp_valid = false;
     const gs::LowpShadow shadow = gs::lowp_shadow(t);
-    gs::clip_sgd_launch(2, goff, t->cfg.params, t->cfg.grads, grad_scale, t->cfg.max_norm, t->cfg.lr, ws,
-                        gs::as_stream(stream), shadow, t->take_done());
+    if (t->opt.kind == GS_OPT_ADAM)
+        gs::adam_update(t, false, grad_scale, ws, gs::as_stream(stream), shadow);
+    else
+        gs::clip_sgd_launch(2, goff, t->cfg.params, t->cfg.grads, grad_scale, t->cfg.max_norm, t->cfg.lr, ws,
+                            gs::as_stream(stream), shadow, t->take_done());
     t->lp_valid = shadow.p != nullptr;
     GS_API_END
 }

@@ -162,6 +162,18 @@ def clip_sgd(goff, params, grads, grad_scale, max_norm, lr, ws):
                             float(max_norm), float(lr), ptr(ws), _stream(params)))
 
 
+def clip_adam(goff, params, grads, m, v, grad_scale, max_norm, lr, betas, eps, weight_decay, step, ws):
+    """gs_clip_adam: clip per group (the clipped gradient stays in `grads`),
+    then one AdamW update of `params` and the moments `m`, `v` in place;
+    `step` >= 1 numbers the update being applied."""
+    import numpy as np
+    _dev(params, grads, m, v, ws)
+    go = np.ascontiguousarray(goff, dtype=np.int64)
+    check(lib().gs_clip_adam(len(go) - 1, ptr(go), ptr(params), ptr(grads), ptr(m), ptr(v), float(grad_scale),
+                             float(max_norm), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                             float(weight_decay), int(step), ptr(ws), _stream(params)))
+
+
 def fill_uniform(X, seed):
     _dev(X)
     check(lib().gs_fill_uniform(ptr(X), _DT[X.dtype], X.shape[0], X.shape[1], X.stride(0),

@@ -58,11 +58,32 @@ class FlatParams:
         return {n: self.view(i).detach().clone() for i, n in enumerate(self.names)}
 
 
+_OPTIMIZERS = {"sgd": _lib.GS_OPT_SGD, "adam": _lib.GS_OPT_ADAM}
+
+
+def optimizer_kind(name):
+    """GS_OPT_* of an optimiser name ("sgd" or "adam"); ValueError otherwise."""
+    try:
+        return _OPTIMIZERS[name]
+    except (KeyError, TypeError):
+        raise ValueError(f"optimizer must be one of {sorted(_OPTIMIZERS)}, got {name!r}") from None
+
+
 class NativeTrainer:
-    """Fused supervised GraphSAGE step on one GPU (one rank of data parallel)."""
+    """Fused supervised GraphSAGE step on one GPU (one rank of data parallel).
+
+    `optimizer`: "sgd" (the reference's clip_grad_norm_(max_norm) + SGD(lr)) or
+    "adam": the same clip, then torch.optim.AdamW's update with `betas`, `eps`
+    and `weight_decay` (Adam at weight_decay = 0) on flat moment buffers beside
+    the parameters.  max_norm = float("inf") disables the clip.  Adam updates
+    are never deferred into the next step: each is a launch of its own."""
 
     def __init__(self, graph, features, labels, n_classes, num_layers=2, hidden=128, fanouts=(10, 10),
-                 agg_func="MEAN", gcn=False, lr=0.7, max_norm=5.0, seed=824, weights=None):
+                 agg_func="MEAN", gcn=False, lr=0.7, max_norm=5.0, seed=824, weights=None, optimizer="sgd",
+                 betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        self.optimizer = optimizer
+        self._opt_kind = optimizer_kind(optimizer)
+        self.betas, self.eps, self.weight_decay = (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
         if not features.is_cuda:
             raise RuntimeError("NativeTrainer runs on a HIP device")
         self.device = features.device
@@ -92,6 +113,45 @@ class NativeTrainer:
         if lib().gs_trainer_n_params(h) != self.p.params.numel():
             raise RuntimeError("flat parameter layout mismatch")
         self._ws = torch.empty(0, dtype=torch.uint8, device=self.device)
+        self.opt_m = self.opt_v = None
+        if self._opt_kind == _lib.GS_OPT_ADAM:
+            self.opt_m = torch.zeros_like(self.p.params)
+            self.opt_v = torch.zeros_like(self.p.params)
+            self._set_optimizer(0)
+
+    def _set_optimizer(self, step):
+        oc = _lib.OptimizerConfig(kind=self._opt_kind, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
+                                  weight_decay=self.weight_decay, m=_lib.ptr(self.opt_m),
+                                  v=_lib.ptr(self.opt_v), step=int(step))
+        check(lib().gs_trainer_set_optimizer(self._h, ctypes.byref(oc)))
+
+    def optimizer_state(self):
+        """{"step", "m", "v"}: the updates applied so far and clones of the
+        flat Adam moments (None under SGD, which keeps no state)."""
+        return {"step": int(lib().gs_trainer_opt_step(self._h)),
+                "m": None if self.opt_m is None else self.opt_m.detach().clone(),
+                "v": None if self.opt_v is None else self.opt_v.detach().clone()}
+
+    def load_optimizer_state(self, state):
+        """Restore optimizer_state() of a trainer with the same optimiser and
+        parameter layout: with the parameters restored too, training continues
+        bit for bit."""
+        if self.opt_m is not None:
+            if state["m"] is None or state["v"] is None:
+                raise ValueError("load_optimizer_state: the state holds no Adam moments")
+            if state["m"].numel() != self.opt_m.numel() or state["v"].numel() != self.opt_v.numel():
+                raise ValueError("load_optimizer_state: moment size != parameter count")
+            self.opt_m.copy_(state["m"].reshape(-1))
+            self.opt_v.copy_(state["v"].reshape(-1))
+        self._set_optimizer(state["step"])
+
+    def load_state_dict(self, sd):
+        """Copy the named parameters of state_dict() back into the flat buffer."""
+        for i, n in enumerate(self.p.names):
+            self.p.view(i).copy_(sd[n])
+
+    def state_dict(self):
+        return self.p.state_dict()
 
     def weights(self):
         return [self.p.view(i) for i in range(self.L)]

@@ -491,6 +491,23 @@ int gs_clip_sgd(int32_t n_groups, const int64_t* goff_host, float* params,
                 float* grads, float grad_scale, float max_norm, float lr,
                 float* ws, void* stream);
 
+/* gs_clip_sgd's clip (per group, grads scaled by `grad_scale` first, the
+ * clipped gradient left in grads), then torch.optim.AdamW's update (Adam at
+ * weight_decay = 0) on the flat buffers, fp32:
+ *   p *= 1 - lr * weight_decay
+ *   m = beta1 * m + (1 - beta1) * g;  v = beta2 * v + (1 - beta2) * g * g
+ *   p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ * m, v: the moments (device, as long as params, caller-owned, zero before the
+ * first update).  step >= 1 numbers the update being applied; both bias
+ * corrections are computed on the host in double.  ws as for gs_clip_sgd.
+ * GS_EINVAL (before any device work): a NULL pointer, n_groups outside 1..8,
+ * unsorted offsets, a beta outside [0, 1), eps <= 0, weight_decay < 0,
+ * step < 1.  max_norm = INFINITY disables the clip. */
+int gs_clip_adam(int32_t n_groups, const int64_t* goff_host, float* params,
+                 float* grads, float* m, float* v, float grad_scale, float max_norm,
+                 float lr, float beta1, float beta2, float eps, float weight_decay,
+                 int64_t step, float* ws, void* stream);
+
 /* f32 → bf16 (RNE) cast, n elements. */
 int gs_cast_f32_bf16(const float* in, void* out, int64_t n, void* stream);
 
@@ -644,6 +661,29 @@ int gs_trainer_defer(gs_trainer* t, int32_t on, int32_t* active, void* stream);
 enum { GS_TOPT_FUSED_BWD = 0, GS_TOPT_TOP_LAUNCH = 1, GS_TOPT_SELF_ROWS = 2, GS_TOPT_DEFER_UPDATE = 3,
        GS_TOPT_TOP_PAIR = 4 };
 int gs_trainer_set_option(gs_trainer* t, int32_t opt, int32_t value);
+/* The optimiser of gs_trainer_update / gs_trainer_update_local (and so of a
+ * runner loop).  GS_OPT_SGD (the default): clip + SGD with cfg.lr, the other
+ * fields ignored.  GS_OPT_ADAM: the clip, then gs_clip_adam's update with
+ * cfg.lr and these hyper-parameters; m, v hold the moments (device,
+ * gs_trainer_n_params floats each, caller-owned, kept until the trainer is
+ * destroyed or the optimiser set again) and `step` the updates already
+ * applied to them (0 for zeroed moments; a resumed run passes the saved
+ * count).  Every applied update adds one to the count (gs_trainer_opt_step).
+ * An Adam update is always a launch of its own: gs_trainer_defer and the
+ * runner's deferred update report "not active" and every update runs at once.
+ * GS_EINVAL: NULL arguments, an unknown kind, hyper-parameters gs_clip_adam
+ * refuses, step < 0, or a call while deferring, with an update pending or
+ * inside a runner loop (gs_trainer_set_option's rule). */
+enum { GS_OPT_SGD = 0, GS_OPT_ADAM = 1 };
+typedef struct {
+    int32_t kind;
+    float beta1, beta2, eps, weight_decay;
+    float* m;
+    float* v;
+    int64_t step;
+} gs_optimizer_config;
+int gs_trainer_set_optimizer(gs_trainer* t, const gs_optimizer_config* oc);
+int64_t gs_trainer_opt_step(const gs_trainer* t);
 
 /* ------------------------------------------------------- RCCL communicator
  * One communicator per data-parallel rank for the gradient all-reduce of the
