@@ -20,6 +20,29 @@ namespace gs {
 
 static_assert(kThreads == kBlock && kThreads == kClsRedThreads, "fused roles share one block size");
 
+// Launch A's roles: the dW row slabs, dIn and (top layer) the classifier reduce.
+struct BwdA {
+    int n, F, H, K, rps;
+    const float* Xs;
+    int64_t ldxs;
+    const int* sidx;
+    const float* A;
+    int64_t lda;    // A's row stride (F, or 2F for the top path's dense [self | agg] rows)
+    const float* dZ;
+    float* target;  // dW slabs (or dW itself when S == 1)
+    int dw_gx, dw_gy, dw_nb;
+    const float* W;
+    float* dSelf;
+    float* dA;
+    int dx_gx, dx_nb;
+    // classifier reduce (top layer only)
+    int B, D, C, cls_rows;
+    const float* cls_slab;
+    float* dWc;
+    float* dbc;
+    float* loss;
+    float* cls_part;
+};
 
 template <bool HAS_SELF, bool ZVEC, bool CLS>
 __global__ __launch_bounds__(kThreads) void layer_bwd_a_kernel(BwdA a) {
@@ -61,18 +84,17 @@ struct BwdB {
     const float* Hprev;
     float* dH;
     const int4* rec = nullptr;  // agg_bwd_rec_body's records (layer_bwd_top only)
-    int64_t off2 = 0;           // dIn as two partials (the top launch's pair form), the second off2 floats on
 };
 
-template <int OP, int G, bool PAIR>
+template <int OP, int G>
 __global__ __launch_bounds__(kThreads) void layer_bwd_b_kernel(BwdB b) {
     const int bx = blockIdx.x;
     if (bx < b.sum_nb) {
         sum_slabs_body(bx, b.sum_nb, b.slabs, b.S, b.len, b.dW, b.part);
         return;
     }
-    agg_bwd_body<OP, 4, G, PAIR>(bx - b.sum_nb, b.n_src, b.F, b.tptr, b.tidx, b.ptr, b.dA, b.dSelf, b.ldd, b.argmax,
-                           b.Hprev, b.F, b.dH, b.off2);
+    agg_bwd_body<OP, 4, G>(bx - b.sum_nb, b.n_src, b.F, b.tptr, b.tidx, b.ptr, b.dA, b.dSelf, b.ldd, b.argmax,
+                           b.Hprev, b.F, b.dH);
 }
 
 struct BwdT {
@@ -81,7 +103,7 @@ struct BwdT {
     int cls_nb;
 };
 
-template <int OP, int G, bool PAIR>
+template <int OP, int G>
 __global__ __launch_bounds__(kThreads) void layer_bwd_top_kernel(BwdT t) {
     int b = blockIdx.x;
     if (b < t.a.dw_nb) {
@@ -100,11 +122,11 @@ __global__ __launch_bounds__(kThreads) void layer_bwd_top_kernel(BwdT t) {
     }
     b -= t.cls_nb;
     if (t.b.rec)
-        agg_bwd_rec_body<OP, 4, G, PAIR>(b, t.b.n_src, t.b.F, t.b.rec, t.b.tidx, t.b.ptr, t.b.dA, t.b.dSelf, t.b.ldd,
-                                   t.b.argmax, t.b.Hprev, t.b.F, t.b.dH, t.b.off2);
+        agg_bwd_rec_body<OP, 4, G>(b, t.b.n_src, t.b.F, t.b.rec, t.b.tidx, t.b.ptr, t.b.dA, t.b.dSelf, t.b.ldd,
+                                   t.b.argmax, t.b.Hprev, t.b.F, t.b.dH);
     else
-        agg_bwd_body<OP, 4, G, PAIR>(b, t.b.n_src, t.b.F, t.b.tptr, t.b.tidx, t.b.ptr, t.b.dA, t.b.dSelf, t.b.ldd,
-                               t.b.argmax, t.b.Hprev, t.b.F, t.b.dH, t.b.off2);
+        agg_bwd_body<OP, 4, G>(b, t.b.n_src, t.b.F, t.b.tptr, t.b.tidx, t.b.ptr, t.b.dA, t.b.dSelf, t.b.ldd,
+                               t.b.argmax, t.b.Hprev, t.b.F, t.b.dH);
 }
 
 int cls_reduce_grid(int64_t C, int64_t D) { return cls_reduce_blocks(C, D); }
@@ -119,14 +141,9 @@ bool layer_bwd_fusable(const LayerBwd& a) {
            a.n < (int64_t(1) << 31) && a.n_src < (int64_t(1) << 31);
 }
 
-int layer_bwd(const LayerBwd& a, const ClsReduce* cls, float* part, hipStream_t st) {
-    GS_REQUIRE(layer_bwd_fusable(a), GS_EINVAL, "layer backward not fusable");
-    const bool self = a.Xs != nullptr;
-    const int64_t K = self ? 2 * a.fin : a.fin;
-    const int S = dw_splits(a.n, K, a.H);
-    const int rps = dw_rows_per_split(a.n, K, a.H);
-    GS_REQUIRE(S == 1 || a.slab_bytes >= static_cast<int64_t>(S) * K * a.H * 4, GS_EINVAL, "workspace too small");
-    BwdA A{};
+
+// The dW-slab role of layer `a` (K input columns) over S row splits of rps rows.
+static void fill_dw(BwdA& A, const LayerBwd& a, int64_t K, int S, int rps) {
     A.n = static_cast<int>(a.n);
     A.F = static_cast<int>(a.fin);
     A.H = static_cast<int>(a.H);
@@ -142,24 +159,56 @@ int layer_bwd(const LayerBwd& a, const ClsReduce* cls, float* part, hipStream_t 
     A.dw_gx = static_cast<int>((K + 63) / 64);
     A.dw_gy = static_cast<int>((a.H + 63) / 64);
     A.dw_nb = A.dw_gx * A.dw_gy * S;
+}
+
+// The classifier-reduce role; returns its blocks.
+static int fill_cls(BwdA& A, const ClsReduce& cls) {
+    A.B = static_cast<int>(cls.B);
+    A.D = static_cast<int>(cls.D);
+    A.C = static_cast<int>(cls.C);
+    A.cls_rows = cls.n_row_blocks;
+    A.cls_slab = cls.slab;
+    A.dWc = cls.dWc;
+    A.dbc = cls.dbc;
+    A.loss = cls.loss;
+    A.cls_part = cls.part;
+    return cls_reduce_blocks(cls.C, cls.D);
+}
+
+// The agg-backward role (dIn = [dSelf | dA], or dA alone when gcn); returns its blocks for groups of G lanes.
+static int fill_agg(BwdB& B, const LayerBwd& a, int64_t K, int G) {
+    B.n_src = static_cast<int>(a.n_src);
+    B.F = static_cast<int>(a.H);
+    B.tptr = a.tptr;
+    B.tidx = a.tidx;
+    B.ptr = a.ptr;
+    B.dSelf = a.Xs ? a.dIn : nullptr;
+    B.dA = a.Xs ? a.dIn + a.fin : a.dIn;
+    B.ldd = K;
+    B.argmax = a.argmax;
+    B.Hprev = a.Hprev;
+    B.dH = a.dH;
+    return static_cast<int>((a.n_src + (kBlock / G) - 1) / (kBlock / G));
+}
+
+int layer_bwd(const LayerBwd& a, const ClsReduce* cls, float* part, hipStream_t st) {
+    GS_REQUIRE(layer_bwd_fusable(a), GS_EINVAL, "layer backward not fusable");
+    const bool self = a.Xs != nullptr;
+    const int64_t K = self ? 2 * a.fin : a.fin;
+    const int S = dw_splits(a.n, K, a.H);
+    const int rps = dw_rows_per_split(a.n, K, a.H);
+    GS_REQUIRE(S == 1 || a.slab_bytes >= static_cast<int64_t>(S) * K * a.H * 4, GS_EINVAL, "workspace too small");
+    const int G = pick_group(static_cast<int>(a.H), 4);
+    BwdB Bq{};
+    const int agg_nb = fill_agg(Bq, a, K, G);
+    BwdA A{};
+    fill_dw(A, a, K, S, rps);
     A.W = a.W;
     A.dSelf = self ? a.dIn : nullptr;
     A.dA = self ? a.dIn + a.fin : a.dIn;
     A.dx_gx = static_cast<int>((a.n + 15) / 16);
     A.dx_nb = a.din_ready ? 0 : A.dx_gx * static_cast<int>((K + 63) / 64);
-    int cls_nb = 0;
-    if (cls) {
-        A.B = static_cast<int>(cls->B);
-        A.D = static_cast<int>(cls->D);
-        A.C = static_cast<int>(cls->C);
-        A.cls_rows = cls->n_row_blocks;
-        A.cls_slab = cls->slab;
-        A.dWc = cls->dWc;
-        A.dbc = cls->dbc;
-        A.loss = cls->loss;
-        A.cls_part = cls->part;
-        cls_nb = cls_reduce_blocks(cls->C, cls->D);
-    }
+    const int cls_nb = cls ? fill_cls(A, *cls) : 0;
     const dim3 ga(static_cast<unsigned>(A.dw_nb + A.dx_nb + cls_nb));
 #define GS_BWDA(SELF, CLS) layer_bwd_a_kernel<SELF, true, CLS><<<ga, kThreads, 0, st>>>(A)
     if (self) {
@@ -172,39 +221,22 @@ int layer_bwd(const LayerBwd& a, const ClsReduce* cls, float* part, hipStream_t 
 #undef GS_BWDA
     check_launch("layer_bwd(A)");
 
-    BwdB Bq{};
     Bq.slabs = a.slabs;
     Bq.S = S;
     Bq.len = a.H * K;
     Bq.dW = a.dW;
     Bq.part = part;
     Bq.sum_nb = S > 1 ? sum_slabs_blocks(Bq.len) : 0;
-    Bq.n_src = static_cast<int>(a.n_src);
-    Bq.F = static_cast<int>(a.H);
-    Bq.tptr = a.tptr;
-    Bq.tidx = a.tidx;
-    Bq.ptr = a.ptr;
-    Bq.dA = A.dA;
-    Bq.dSelf = A.dSelf;
-    Bq.ldd = K;
-    Bq.argmax = a.argmax;
-    Bq.Hprev = a.Hprev;
-    Bq.dH = a.dH;
-    Bq.off2 = a.din_off2;
-    const int G = pick_group(static_cast<int>(a.H), 4);
-    const int agg_nb = static_cast<int>((a.n_src + (kBlock / G) - 1) / (kBlock / G));
     const dim3 gb(static_cast<unsigned>(Bq.sum_nb + agg_nb));
-#define GS_BWDB2(OP, PR)                                                                    \
-    do {                                                                                    \
-        if (G == 16) layer_bwd_b_kernel<OP, 16, PR><<<gb, kThreads, 0, st>>>(Bq);           \
-        else if (G == 32) layer_bwd_b_kernel<OP, 32, PR><<<gb, kThreads, 0, st>>>(Bq);      \
-        else layer_bwd_b_kernel<OP, 64, PR><<<gb, kThreads, 0, st>>>(Bq);                   \
+#define GS_BWDB(OP)                                                                   \
+    do {                                                                              \
+        if (G == 16) layer_bwd_b_kernel<OP, 16><<<gb, kThreads, 0, st>>>(Bq);         \
+        else if (G == 32) layer_bwd_b_kernel<OP, 32><<<gb, kThreads, 0, st>>>(Bq);    \
+        else layer_bwd_b_kernel<OP, 64><<<gb, kThreads, 0, st>>>(Bq);                 \
     } while (0)
-#define GS_BWDB(OP) do { if (Bq.off2) GS_BWDB2(OP, true); else GS_BWDB2(OP, false); } while (0)
     if (a.agg == GS_AGG_MEAN) GS_BWDB(GS_AGG_MEAN);
     else GS_BWDB(GS_AGG_MAX);
 #undef GS_BWDB
-#undef GS_BWDB2
     check_launch("layer_bwd(B)");
     return Bq.sum_nb;
 }
@@ -215,61 +247,22 @@ int layer_bwd_top(const LayerBwd& a, const ClsReduce& cls, SlabSum* deferred, hi
     const int S = dw_splits(a.n, K, a.H);
     const int rps = dw_rows_per_split(a.n, K, a.H);
     GS_REQUIRE(S == 1 || a.slab_bytes >= static_cast<int64_t>(S) * K * a.H * 4, GS_EINVAL, "workspace too small");
-    BwdT t{};
-    BwdA& A = t.a;
-    A.n = static_cast<int>(a.n);
-    A.F = static_cast<int>(a.fin);
-    A.H = static_cast<int>(a.H);
-    A.K = static_cast<int>(K);
-    A.rps = rps;
-    A.Xs = a.Xs;
-    A.ldxs = a.ldxs;
-    A.sidx = a.sidx;
-    A.A = a.A;
-    A.lda = a.lda > 0 ? a.lda : a.fin;
-    A.dZ = a.dZ;
-    A.target = S > 1 ? a.slabs : a.dW;
-    A.dw_gx = static_cast<int>((K + 63) / 64);
-    A.dw_gy = static_cast<int>((a.H + 63) / 64);
-    A.dw_nb = A.dw_gx * A.dw_gy * S;
-    A.B = static_cast<int>(cls.B);
-    A.D = static_cast<int>(cls.D);
-    A.C = static_cast<int>(cls.C);
-    A.cls_rows = cls.n_row_blocks;
-    A.cls_slab = cls.slab;
-    A.dWc = cls.dWc;
-    A.dbc = cls.dbc;
-    A.loss = cls.loss;
-    A.cls_part = cls.part;
-    t.cls_nb = cls_reduce_blocks(cls.C, cls.D);
-    BwdB& Bq = t.b;
-    Bq.n_src = static_cast<int>(a.n_src);
-    Bq.F = static_cast<int>(a.H);
-    Bq.tptr = a.tptr;
-    Bq.tidx = a.tidx;
-    Bq.ptr = a.ptr;
-    Bq.dSelf = a.dIn;
-    Bq.dA = a.dIn + a.fin;
-    Bq.ldd = K;
-    Bq.argmax = a.argmax;
-    Bq.Hprev = a.Hprev;
-    Bq.dH = a.dH;
-    Bq.off2 = a.din_off2;
-    Bq.rec = a.trec;
     const int G = pick_group(static_cast<int>(a.H), 4);
-    const int agg_nb = static_cast<int>((a.n_src + (kBlock / G) - 1) / (kBlock / G));
-    const dim3 grid(static_cast<unsigned>(A.dw_nb + t.cls_nb + agg_nb));
-#define GS_BWDT2(OP, PR)                                                                \
+    BwdT t{};
+    fill_dw(t.a, a, K, S, rps);
+    t.cls_nb = fill_cls(t.a, cls);
+    const int agg_nb = fill_agg(t.b, a, K, G);
+    t.b.rec = a.trec;
+    const dim3 grid(static_cast<unsigned>(t.a.dw_nb + t.cls_nb + agg_nb));
+#define GS_BWDT(OP)                                                                     \
     do {                                                                                \
-        if (G == 16) layer_bwd_top_kernel<OP, 16, PR><<<grid, kThreads, 0, st>>>(t);    \
-        else if (G == 32) layer_bwd_top_kernel<OP, 32, PR><<<grid, kThreads, 0, st>>>(t); \
-        else layer_bwd_top_kernel<OP, 64, PR><<<grid, kThreads, 0, st>>>(t);            \
+        if (G == 16) layer_bwd_top_kernel<OP, 16><<<grid, kThreads, 0, st>>>(t);        \
+        else if (G == 32) layer_bwd_top_kernel<OP, 32><<<grid, kThreads, 0, st>>>(t);   \
+        else layer_bwd_top_kernel<OP, 64><<<grid, kThreads, 0, st>>>(t);                \
     } while (0)
-#define GS_BWDT(OP) do { if (t.b.off2) GS_BWDT2(OP, true); else GS_BWDT2(OP, false); } while (0)
     if (a.agg == GS_AGG_MEAN) GS_BWDT(GS_AGG_MEAN);
     else GS_BWDT(GS_AGG_MAX);
 #undef GS_BWDT
-#undef GS_BWDT2
     check_launch("layer_bwd_top");
     *deferred = SlabSum{a.slabs, S, a.H * K, a.dW, nullptr};
     return S > 1 ? sum_slabs_pair_parts2(a.H * K) : 0;

@@ -162,7 +162,7 @@ inline void check_launch(const char* what) {
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
-// In-kernel span of a timed launch (the bench's roofline timers, step.hip): a
+// In-kernel span of a timed launch (the bench's roofline timers, step_timer.hip): a
 // kernel that supports it (the layer-1 wide forward, the dW GEMM, the top
 // launch, the slab-sum pair) stores the 100 MHz s_memrealtime clock at each
 // workgroup's start and end (plain stores, one slot per workgroup: no
@@ -217,7 +217,7 @@ struct LowpShadow {
 };
 
 // A clip + SGD left pending by the previous step (gs_trainer in deferred-update
-// mode, step.hip), applied by the layer-1 forward launch it is passed to (the
+// mode, step_update.hip), applied by the layer-1 forward launch it is passed to (the
 // wide kernel).  The step's last slab sum wrote S = W1 - lr·G1, W1's update
 // when the clip coefficient of its group is 1; every workgroup of the forward
 // folds the norm partials itself and reads S as W1 when it is, else writes
