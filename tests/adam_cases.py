@@ -67,16 +67,17 @@ def torch_adamw(p, g, m, v, t, lr, betas, eps, wd, goff, scale, max_norm, dtype)
             cat([opt.state[q]["exp_avg_sq"] for q in params]))
 
 
-def check_rule(what, got, ref, tor, figures=None):
+def check_rule(what, got, ref, tor, figures=None, factor=4.0):
     """The tolerance rule of the GPU tests: with e_torch the largest error of
     fp32 torch (tor) against the float64 reference (ref), the kernel's largest
     error must stay within 4 * e_torch + 2^-23 * max|ref|.  The observed ratio
-    err / e_torch goes into the message (and into `figures`)."""
+    err / e_torch goes into the message (and into `figures`).  `factor`: the 4
+    of the rule, for a caller that states why its case needs another."""
     got = np.asarray(got, dtype=np.float64).reshape(-1)
     assert np.all(np.isfinite(got)), f"{what}: NaN or Inf"
     err = float(np.max(np.abs(got - ref))) if got.size else 0.0
     e_torch = float(np.max(np.abs(tor - ref))) if got.size else 0.0
-    bound = 4.0 * e_torch + 2.0 ** -23 * (float(np.max(np.abs(ref))) if got.size else 0.0)
+    bound = factor * e_torch + 2.0 ** -23 * (float(np.max(np.abs(ref))) if got.size else 0.0)
     ratio = err / e_torch if e_torch > 0 else (0.0 if err == 0 else float("inf"))
     msg = f"{what}: err {err:.3e}, e_torch {e_torch:.3e}, err/e_torch {ratio:.2f}, bound {bound:.3e}"
     print(msg)

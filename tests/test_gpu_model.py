@@ -1,7 +1,14 @@
 """Model-level parity on the MI355X: the drop-in GraphSage / SageLayer against
 the reference's golden vectors (embeddings within 1e-5 fp32, weight gradients,
 RNG stream position) and against the oracle on the benchmark's fanouts; the
-native fused training step against the oracle's training step."""
+native fused training step against the oracle's training step.
+
+Every NativeTrainer here has hidden 128, and all but a few two layers: the
+switch tests (fused / unfused, top launch / separate launches, self_rows,
+runner / Python loop) compare two paths that share the kernels under them.
+The step at other hidden sizes, layer counts, feature widths and class
+counts, against an independent float64 reference, is test_gpu_step_matrix.py
+(shapes in step_cases.py, reference in step_ref.py)."""
 import importlib
 import os
 import random
