@@ -181,7 +181,33 @@ _SIGS = {
     "gs_dsampler_debug": (_i32, [_vp, _vp, _i32]),
     "gs_dsampler_set_seed": (_i32, [_vp, _u64]),
     "gs_dsampler_run_at": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "gs_full_plan_create": (_i32, [_vp, _vp, _i64, _i32, _i64, _p(_vp)]),
+    "gs_full_plan_destroy": (None, [_vp]),
+    "gs_full_plan_dims": (_i32, [_vp, _vp]),
+    "gs_full_plan_array": (_vp, [_vp, _i32]),
+    "gs_agg_full_ws_bytes": (_i64, [_vp, _i64, _i64, _i64]),
+    "gs_agg_full": (_i32, [_vp, _vp, _i32, _i32, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64,
+                           _vp]),
+    "gs_infer_full_ws_bytes": (_i64, [_vp, _vp]),
+    "gs_infer_full": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
 }
+
+(GS_FP_N_NODES, GS_FP_N_ITEMS, GS_FP_N_SLOTS, GS_FP_N_SPLIT, GS_FP_N_EMPTY, GS_FP_SEG_LEN, GS_FP_GCN,
+ GS_FP_N_ENTRIES, GS_FP_NDIMS) = range(9)
+(GS_FP_ITEMS, GS_FP_ITEM_PTR, GS_FP_SLOT_PTR, GS_FP_SPLIT_PTR, GS_FP_SPLIT_ROWS, GS_FP_COUNT, GS_FP_SELF_LOOP,
+ GS_FP_EMPTY_ROWS) = range(8)
+
+
+class FullPlanDev(ctypes.Structure):
+    _fields_ = [("items", _vp), ("slot_ptr", _vp), ("split_rows", _vp), ("count", _vp), ("self_loop", _vp)]
+
+
+class InferFullConfig(ctypes.Structure):
+    _fields_ = [
+        ("n_layers", _i32), ("hidden", _i32), ("agg", _i32), ("feat_dtype", _i32),
+        ("feat_dim", _i64), ("feat_ld", _i64), ("X", _vp), ("row_ptr", _vp), ("col", _vp),
+        ("W", _vp * GS_MAX_HOPS), ("chunk_rows", _i64),
+    ]
 
 
 class TrainerConfig(ctypes.Structure):

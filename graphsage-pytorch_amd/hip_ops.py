@@ -54,6 +54,147 @@ def agg_fwd(agg_func, X, ptr_, idx, out, *, row_ptr=None, col=None, dst_ids=None
     return out
 
 
+# Defaults of the full-neighbourhood path, the fastest measured on rmat2m
+# (profiles/full_infer_bench.json, DESIGN §4 "Exact full-neighbourhood
+# inference"): rows longer than 256 entries are reduced in segments, and the
+# driver works in chunks of 2 Mi rows (rmat2m as one chunk: smaller chunks
+# were slower, larger graphs keep the chunk buffer at this size).
+FULL_SEG_LEN = 256
+FULL_CHUNK_ROWS = 1 << 21
+
+
+class FullPlan:
+    """The work plan of agg_full (gs_full_plan): built on the host once per
+    graph, gcn flag and seg_len (None: FULL_SEG_LEN; <= 0: no row is split).
+    `graph` is a CSRGraph or a (row_ptr int64, col int32) pair of numpy arrays.
+    The host arrays are readable without a GPU (array()); device() uploads the
+    ones the kernels read, once per device."""
+
+    _DTYPES = {_lib.GS_FP_ITEMS: "int32", _lib.GS_FP_ITEM_PTR: "int64", _lib.GS_FP_SLOT_PTR: "int64",
+               _lib.GS_FP_SPLIT_PTR: "int64", _lib.GS_FP_SPLIT_ROWS: "int32", _lib.GS_FP_COUNT: "int32",
+               _lib.GS_FP_SELF_LOOP: "uint8", _lib.GS_FP_EMPTY_ROWS: "int32"}
+
+    def __init__(self, graph, gcn=False, seg_len=None):
+        import ctypes
+
+        import numpy as np
+        if isinstance(graph, tuple):
+            row_ptr, col = graph
+            self.graph = None
+        else:
+            row_ptr, col = graph.row_ptr(), graph.col()
+            self.graph = graph
+        self.row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        self.col = np.ascontiguousarray(col, dtype=np.int32)
+        if self.row_ptr.ndim != 1 or len(self.row_ptr) < 1 or self.col.ndim != 1 or \
+                len(self.col) < int(self.row_ptr[-1]):
+            raise ValueError("FullPlan: row_ptr [n + 1] and col [row_ptr[n]] expected")
+        seg_len = FULL_SEG_LEN if seg_len is None else int(seg_len)
+        h = ctypes.c_void_p()
+        check(lib().gs_full_plan_create(ptr(self.row_ptr), ptr(self.col), len(self.row_ptr) - 1, int(bool(gcn)),
+                                        seg_len, ctypes.byref(h)))
+        self._h = h
+        dims = np.zeros(_lib.GS_FP_NDIMS, np.int64)
+        check(lib().gs_full_plan_dims(h, ptr(dims)))
+        self.n_nodes, self.n_items, self.n_slots, self.n_split, self.n_empty, self.seg_len = \
+            (int(dims[i]) for i in (_lib.GS_FP_N_NODES, _lib.GS_FP_N_ITEMS, _lib.GS_FP_N_SLOTS, _lib.GS_FP_N_SPLIT,
+                                    _lib.GS_FP_N_EMPTY, _lib.GS_FP_SEG_LEN))
+        self.gcn = bool(dims[_lib.GS_FP_GCN])
+        self.n_entries = int(dims[_lib.GS_FP_N_ENTRIES])
+        self._dev = {}
+
+    def array(self, which):
+        """A copy of one of the plan's host arrays (a _lib.GS_FP_* array id)."""
+        import ctypes
+
+        import numpy as np
+        n = {_lib.GS_FP_ITEMS: 2 * self.n_items, _lib.GS_FP_ITEM_PTR: self.n_nodes + 1,
+             _lib.GS_FP_SLOT_PTR: self.n_nodes + 1, _lib.GS_FP_SPLIT_PTR: self.n_nodes + 1,
+             _lib.GS_FP_SPLIT_ROWS: self.n_split, _lib.GS_FP_COUNT: self.n_nodes,
+             _lib.GS_FP_SELF_LOOP: self.n_nodes, _lib.GS_FP_EMPTY_ROWS: self.n_empty}[which]
+        dt = np.dtype(self._DTYPES[which])
+        if n == 0:
+            return np.zeros(0, dt)
+        p = lib().gs_full_plan_array(self._h, which)
+        buf = (ctypes.c_char * (n * dt.itemsize)).from_address(p)
+        a = np.frombuffer(buf, dtype=dt).copy()
+        return a.reshape(-1, 2) if which == _lib.GS_FP_ITEMS else a
+
+    def device(self, device):
+        """(gs_full_plan_dev, row_ptr, col) on `device`; the tensors stay alive with the plan."""
+        key = str(torch.device(device))
+        if key not in self._dev:
+            ts = {w: torch.from_numpy(self.array(w).reshape(-1)).to(device)
+                  for w in (_lib.GS_FP_ITEMS, _lib.GS_FP_SLOT_PTR, _lib.GS_FP_SPLIT_ROWS, _lib.GS_FP_COUNT,
+                            _lib.GS_FP_SELF_LOOP)}
+            if self.graph is not None:
+                rp, cl = self.graph.device_csr(device)
+            else:
+                rp = torch.from_numpy(self.row_ptr).to(device)
+                cl = torch.from_numpy(self.col).to(device)
+                if cl.numel() == 0:
+                    cl = torch.zeros(1, dtype=torch.int32, device=device)
+            d = _lib.FullPlanDev(items=ptr(ts[_lib.GS_FP_ITEMS]), slot_ptr=ptr(ts[_lib.GS_FP_SLOT_PTR]),
+                                 split_rows=ptr(ts[_lib.GS_FP_SPLIT_ROWS]) if self.n_split else None,
+                                 count=ptr(ts[_lib.GS_FP_COUNT]), self_loop=ptr(ts[_lib.GS_FP_SELF_LOOP]))
+            self._dev[key] = (d, rp, cl, ts)
+        return self._dev[key][:3]
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and getattr(_lib, "_lib", None) is not None:
+            _lib._lib.gs_full_plan_destroy(h)
+            self._h = None
+
+
+def agg_full(agg_func, X, graph, out=None, *, gcn=False, seg_len=None, row0=0, n_rows=None, ws=None):
+    """Full-neighbourhood mean/max of rows of X over the device CSR for the
+    destination rows [row0, row0 + n_rows) (gs_agg_full): adj[v] without v, or
+    with v exactly once under gcn; rows longer than `seg_len` entries are
+    reduced in segments (None: FULL_SEG_LEN; <= 0: never).  `graph` is a
+    CSRGraph (its plan for (gcn, seg_len) is built once and kept on it) or a
+    FullPlan, whose own gcn and seg_len then hold.  out: [n_rows, F] in X's
+    dtype.  MEAN of an empty neighbourhood is a NaN row; MAX over a window
+    that holds one raises IndexError before any launch."""
+    _dev(X, out, ws)
+    import ctypes
+    plan = graph if isinstance(graph, FullPlan) else agg_full_plan(graph, gcn=gcn, seg_len=seg_len)
+    if X.dtype not in _DT:
+        raise TypeError("X must be float32 or bfloat16")
+    if X.dim() != 2 or X.stride(1) != 1 or X.shape[0] < plan.n_nodes:
+        raise ValueError("X must be [n_nodes, F] with unit column stride")
+    n_rows = plan.n_nodes - row0 if n_rows is None else int(n_rows)
+    row0 = int(row0)
+    F = X.shape[1]
+    need = int(lib().gs_agg_full_ws_bytes(plan.handle, F, row0, n_rows))
+    if need < 0:
+        check(_lib.GS_EINVAL)
+    if out is None:
+        out = torch.empty(n_rows, F, dtype=X.dtype, device=X.device)
+    if out.dtype != X.dtype or out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < n_rows or out.shape[1] < F:
+        raise ValueError("out must be [n_rows, F] in X's dtype")
+    if ws is None:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=X.device)
+    d, rp, cl = plan.device(X.device)
+    check(lib().gs_agg_full(plan.handle, ctypes.byref(d), agg_op(agg_func), _DT[X.dtype], ptr(X), X.stride(0), F,
+                            ptr(rp), ptr(cl), row0, n_rows, ptr(out), out.stride(0), ptr(ws),
+                            ws.numel() * ws.element_size(), _stream(X)))
+    return out
+
+
+def agg_full_plan(graph, *, gcn=False, seg_len=None):
+    """The FullPlan of a CSRGraph for (gcn, seg_len), built once per graph."""
+    key = (bool(gcn), FULL_SEG_LEN if seg_len is None else int(seg_len))
+    plans = graph.__dict__.setdefault("_full_plans", {})
+    if key not in plans:
+        plans[key] = FullPlan(graph, gcn=key[0], seg_len=key[1])
+    return plans[key]
+
+
 def sage_linear_fwd(A, Wd, out, *, Xs=None, sidx=None, relu=True):
     """relu([Xs[sidx] | A] · Wᵀ) (models.py:209-220); Xs=None is the gcn form."""
     _dev(A, Wd, out, Xs)

@@ -603,3 +603,67 @@ class Embedder:
                 raise IndexError("MAX aggregation over an empty neighbourhood (reference: models.py:321-325)")
             self.trainer.forward(DeviceSample(s, self.trainer.device), out[n_full * batch:])
         return out
+
+
+class FullEmbedder:
+    """Exact embeddings over full neighbourhoods: the reference's
+    num_sample=None branch (models.py:280-289) for every node, computed layer
+    by layer over the device CSR (gs_infer_full) -- H_1 for all N nodes from
+    the features, H_2 from H_1, ... -- with no sampler, no pack and no
+    `random` stream.  The result does not depend on a batch size, and it is
+    bitwise the same for every `chunk_rows` and from run to run.
+
+    `weights`: the SageLayer weights, layer 1 first.  bf16 features: layer 1
+    runs in bf16 (its aggregate rounded to bf16, W1 cast to bf16), the layers
+    above in fp32.  MEAN gives a node without neighbours a NaN aggregate, as
+    the reference's 0/0; MAX raises IndexError here, at construction, when any
+    node's neighbourhood is empty (as Embedder does when it samples one).
+    `seg_len` / `chunk_rows`: None takes the measured defaults
+    (hip_ops.FULL_SEG_LEN, FULL_CHUNK_ROWS).  Single GPU, inference only."""
+
+    def __init__(self, graph, features, weights, agg_func="MEAN", gcn=False, seg_len=None, chunk_rows=None):
+        self.agg, self.gcn = agg_func, bool(gcn)
+        op = ops.agg_op(agg_func)
+        self.plan = ops.agg_full_plan(graph, gcn=gcn, seg_len=seg_len)
+        if agg_func == "MAX" and self.plan.n_empty:
+            raise IndexError(f"MAX aggregation over an empty neighbourhood ({self.plan.n_empty} nodes have none; "
+                             "reference: models.py:321-325)")
+        if not features.is_cuda:
+            raise RuntimeError("FullEmbedder runs on a HIP device")
+        if features.dim() != 2 or features.stride(1) != 1 or features.shape[0] != graph.n_nodes or \
+                features.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("features must be [n_nodes, F] fp32 or bf16 with unit column stride")
+        self.graph, self.X, self.device = graph, features, features.device
+        self.W = [w.detach().to(device=self.device, dtype=torch.float32).contiguous() for w in weights]
+        self.L, self.H, F = len(self.W), int(self.W[0].shape[0]), features.shape[1]
+        m = 1 if gcn else 2
+        for l, w in enumerate(self.W):
+            if tuple(w.shape) != (self.H, m * (F if l == 0 else self.H)):
+                raise ValueError(f"weights[{l}] must be [{self.H}, {m * (F if l == 0 else self.H)}]")
+        self.chunk_rows = ops.FULL_CHUNK_ROWS if chunk_rows is None else int(chunk_rows)
+        self._dev, self.row_ptr, self.col = self.plan.device(self.device)
+        self.cfg = _lib.InferFullConfig(
+            n_layers=self.L, hidden=self.H, agg=op,
+            feat_dtype=_lib.GS_BF16 if features.dtype == torch.bfloat16 else _lib.GS_F32, feat_dim=F,
+            feat_ld=features.stride(0), X=features.data_ptr(), row_ptr=self.row_ptr.data_ptr(),
+            col=self.col.data_ptr(), chunk_rows=self.chunk_rows)
+        for l, w in enumerate(self.W):
+            self.cfg.W[l] = w.data_ptr()
+        need = int(lib().gs_infer_full_ws_bytes(self.plan.handle, ctypes.byref(self.cfg)))
+        if need < 0:
+            check(_lib.GS_EINVAL)
+        self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+        self._ws_off = (-self._ws.data_ptr()) % 256
+        self._ws_bytes = need
+
+    def embed(self, nodes=None):
+        """[N, hidden] fp32 embeddings on the device (row v = node v), or the
+        rows `nodes` of them."""
+        out = torch.empty(self.graph.n_nodes, self.H, dtype=torch.float32, device=self.device)
+        check(lib().gs_infer_full(self.plan.handle, ctypes.byref(self._dev), ctypes.byref(self.cfg), out.data_ptr(),
+                                  out.stride(0), self._ws.data_ptr() + self._ws_off, self._ws_bytes,
+                                  _lib.stream_ptr(self.device)))
+        if nodes is None:
+            return out
+        idx = torch.from_numpy(np.ascontiguousarray(nodes, dtype=np.int64).reshape(-1)).to(self.device)
+        return out.index_select(0, idx)

@@ -150,7 +150,8 @@ def _embed_ids(gnn_model, ids, b_sz, rngs):
     return emb.embed(ids, b_sz, rngs)
 
 
-def get_gnn_embeddings(gnn_model, dataCenter, ds, b_sz=500, *, sampler_streams=None, group=None, seed=None):
+def get_gnn_embeddings(gnn_model, dataCenter, ds, b_sz=500, *, sampler_streams=None, group=None, seed=None,
+                       full_neighbourhood=False):
     """Embeddings of every node, utils.py:59-78 (batches of 500, in id order).
 
     Default (one process, no `sampler_streams`): the reference's loop — one
@@ -164,9 +165,24 @@ def get_gnn_embeddings(gnn_model, dataCenter, ds, b_sz=500, *, sampler_streams=N
     same state afterwards as the default loop), or the module's own `rng`
     when it was given one; otherwise stream (r, w) is
     seeded train.rank_seed(seed, r, w) (seed defaults to 824), each one a
-    reference stream on its own."""
+    reference stream on its own.
+
+    `full_neighbourhood=True`: exact embeddings over every node's whole
+    neighbourhood (train.FullEmbedder: the reference's num_sample=None branch,
+    layer by layer over all nodes) instead of sampled ones.  Nothing is
+    sampled, so `b_sz`, `sampler_streams` and `seed` are ignored and no
+    `random` state is touched.  One process only: raises on world > 1."""
     n = len(getattr(dataCenter, ds + "_labels"))
     rank, world = _world(group)
+    if full_neighbourhood:
+        if world > 1:
+            raise RuntimeError("get_gnn_embeddings(full_neighbourhood=True) runs on one GPU (world == 1)")
+        from .train import FullEmbedder
+        weights = [getattr(gnn_model, f"sage_layer{i}").weight for i in range(1, gnn_model.num_layers + 1)]
+        X = gnn_model.raw_features
+        X = X if X.is_contiguous() else X.contiguous()
+        emb = FullEmbedder(gnn_model.graph, X, weights, gnn_model.agg_func, gnn_model.gcn)
+        return emb.embed(None if n == gnn_model.graph.n_nodes else np.arange(n, dtype=np.int64)).detach()
     if world == 1 and not sampler_streams:
         out = []
         with torch.no_grad():

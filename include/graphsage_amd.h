@@ -799,6 +799,89 @@ int gs_runner_progress(const gs_runner* r, int64_t* sampled, int64_t* consumed);
 int gs_runner_sync_rngs(gs_runner* r);
 void gs_runner_destroy(gs_runner* r);
 
+/* ------------------------------------- exact full-neighbourhood inference
+ * The reference's num_sample=None branch (models.py:280-289) for every node,
+ * layer by layer over the device CSR: H_1 for all N rows from X, H_2 from H_1,
+ * ...  No sampler, no pack, no random stream.  Single GPU, inference only.
+ *
+ * The plan (host, once per graph, gcn flag and seg_len): destination row v
+ * becomes max(1, ceil(deg(v) / seg_len)) work items (v, s), item s covering
+ * entries [row_ptr[v] + s*seg_len, min(.. + seg_len, row_ptr[v+1])).  Rows of
+ * more than seg_len entries are split: each of their items owns one fp32
+ * partial slot (numbered in item order) and a second pass combines the slots
+ * of a row in segment order.  seg_len <= 0: no row is split.  Per row the
+ * plan records the self-loop flag and the effective neighbour count
+ * (adj[v] \ {v}; adj[v] U {v} under gcn), and it lists the rows whose
+ * effective neighbourhood is empty.  Column ids outside [0, n) are GS_ERANGE. */
+typedef struct gs_full_plan gs_full_plan;
+int gs_full_plan_create(const int64_t* row_ptr, const int32_t* col, int64_t n_nodes,
+                        int32_t gcn, int64_t seg_len, gs_full_plan** out);
+void gs_full_plan_destroy(gs_full_plan* plan);
+/* dims[GS_FP_NDIMS] */
+enum { GS_FP_N_NODES = 0, GS_FP_N_ITEMS, GS_FP_N_SLOTS, GS_FP_N_SPLIT, GS_FP_N_EMPTY,
+       GS_FP_SEG_LEN, GS_FP_GCN, GS_FP_N_ENTRIES, GS_FP_NDIMS };
+int gs_full_plan_dims(const gs_full_plan* plan, int64_t* dims);
+/* The plan's host arrays (owned by the plan):
+ *   ITEMS      int32 [n_items][2]  (row, segment)
+ *   ITEM_PTR   int64 [n + 1]       first item of each row
+ *   SLOT_PTR   int64 [n + 1]       partial slots before each row
+ *   SPLIT_PTR  int64 [n + 1]       split rows before each row
+ *   SPLIT_ROWS int32 [n_split]     ascending
+ *   COUNT      int32 [n]           effective neighbour count
+ *   SELF_LOOP  uint8 [n]           the row holds its own id
+ *   EMPTY_ROWS int32 [n_empty]     rows with COUNT == 0, ascending */
+enum { GS_FP_ITEMS = 0, GS_FP_ITEM_PTR, GS_FP_SLOT_PTR, GS_FP_SPLIT_PTR, GS_FP_SPLIT_ROWS,
+       GS_FP_COUNT, GS_FP_SELF_LOOP, GS_FP_EMPTY_ROWS };
+const void* gs_full_plan_array(const gs_full_plan* plan, int32_t which);
+
+/* Device copies of the arrays the kernels read (uploaded by the caller). */
+typedef struct {
+    const int32_t* items;
+    const int64_t* slot_ptr;
+    const int32_t* split_rows;
+    const int32_t* count;
+    const uint8_t* self_loop;
+} gs_full_plan_dev;
+
+/* Full-neighbourhood aggregate of destination rows [row0, row0 + n_rows):
+ *   out[v - row0] = MEAN / MAX of X[u] over u in adj[v] \ {v}  (gcn: U {v},
+ * self exactly once), read straight from the device CSR (row_ptr int64, col
+ * int32, 64-bit entry offsets).  fp32 accumulation, out in X's dtype.  Rows
+ * of at most seg_len entries are written directly; a longer row's segments
+ * go to fp32 partials in ws (gs_agg_full_ws_bytes) and are combined in
+ * segment order by a second launch: no atomics, the result is a pure function
+ * of the inputs and seg_len.  MEAN of an empty neighbourhood is a NaN row;
+ * MAX over a window that holds one is GS_EEMPTY before any launch. */
+int64_t gs_agg_full_ws_bytes(const gs_full_plan* plan, int64_t F, int64_t row0, int64_t n_rows);
+int gs_agg_full(const gs_full_plan* plan, const gs_full_plan_dev* dev, gs_agg op, gs_dtype dt,
+                const void* X, int64_t ldx, int64_t F, const int64_t* row_ptr, const int32_t* col,
+                int64_t row0, int64_t n_rows, void* out, int64_t ldo,
+                void* ws, int64_t ws_bytes, void* stream);
+
+/* The layer-wise driver: for layer l = 1..n_layers and chunks of chunk_rows
+ * nodes, gs_agg_full of the chunk over H_{l-1} (H_0 = X), then
+ * gs_sage_linear_fwd with the chunk's own rows as self rows (none under the
+ * plan's gcn) into the chunk's rows of H_l (fp32).  bf16 features: layer 1
+ * runs in bf16 (aggregate rounded to bf16, W[0] cast to bf16 into ws), the
+ * layers above in fp32.  out receives H_L, [n][hidden], row stride ldo.
+ * W[l]: fp32 [hidden][K_l], K_1 = feat_dim (x2 without gcn), K_l = hidden
+ * (x2).  1-8 layers, hidden a multiple of 16 in [16, 256].  chunk_rows <= 0:
+ * one chunk.  ws: gs_infer_full_ws_bytes bytes, 256-byte aligned. */
+typedef struct {
+    int32_t n_layers, hidden;
+    int32_t agg;             /* gs_agg */
+    int32_t feat_dtype;      /* gs_dtype */
+    int64_t feat_dim, feat_ld;
+    const void* X;
+    const int64_t* row_ptr;  /* device CSR */
+    const int32_t* col;
+    const float* W[GS_MAX_HOPS];
+    int64_t chunk_rows;
+} gs_infer_full_config;
+int64_t gs_infer_full_ws_bytes(const gs_full_plan* plan, const gs_infer_full_config* cfg);
+int gs_infer_full(const gs_full_plan* plan, const gs_full_plan_dev* dev, const gs_infer_full_config* cfg,
+                  float* out, int64_t ldo, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
