@@ -190,12 +190,24 @@ _SIGS = {
                            _vp]),
     "gs_infer_full_ws_bytes": (_i64, [_vp, _vp]),
     "gs_infer_full": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "gs_full_plan_transpose": (_i32, [_vp, _vp, _vp, _i64, _p(_vp)]),
+    "gs_agg_full_argmax_ws_bytes": (_i64, [_vp, _i64, _i64, _i64]),
+    "gs_agg_full_argmax": (_i32, [_vp, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp,
+                                  _i64, _vp]),
+    "gs_agg_full_bwd_ws_bytes": (_i64, [_vp, _i64]),
+    "gs_agg_full_bwd": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64,
+                               _vp]),
+    "gs_train_full_ws_offset": (_i64, [_vp, _vp, _vp, _i32, _i32]),
+    "gs_train_full_ws_bytes": (_i64, [_vp, _vp, _vp]),
+    "gs_train_full_forward_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),
 }
 
 (GS_FP_N_NODES, GS_FP_N_ITEMS, GS_FP_N_SLOTS, GS_FP_N_SPLIT, GS_FP_N_EMPTY, GS_FP_SEG_LEN, GS_FP_GCN,
  GS_FP_N_ENTRIES, GS_FP_NDIMS) = range(9)
 (GS_FP_ITEMS, GS_FP_ITEM_PTR, GS_FP_SLOT_PTR, GS_FP_SPLIT_PTR, GS_FP_SPLIT_ROWS, GS_FP_COUNT, GS_FP_SELF_LOOP,
  GS_FP_EMPTY_ROWS) = range(8)
+GS_FP_T_ROW_PTR, GS_FP_T_COL = 8, 9  # a transposed plan's own CSR (gs_full_plan_transpose)
+GS_TF_FORWARD, GS_TF_HEAD, GS_TF_BACKWARD, GS_TF_ALL = 1, 2, 4, 7
 
 
 class FullPlanDev(ctypes.Structure):
@@ -207,6 +219,14 @@ class InferFullConfig(ctypes.Structure):
         ("n_layers", _i32), ("hidden", _i32), ("agg", _i32), ("feat_dtype", _i32),
         ("feat_dim", _i64), ("feat_ld", _i64), ("X", _vp), ("row_ptr", _vp), ("col", _vp),
         ("W", _vp * GS_MAX_HOPS), ("chunk_rows", _i64),
+    ]
+
+
+class TrainFullConfig(ctypes.Structure):
+    _fields_ = [
+        ("n_layers", _i32), ("hidden", _i32), ("n_classes", _i32), ("agg", _i32), ("feat_dtype", _i32),
+        ("pad_", _i32), ("feat_dim", _i64), ("feat_ld", _i64), ("max_nodes", _i64), ("X", _vp), ("row_ptr", _vp),
+        ("col", _vp), ("t_row_ptr", _vp), ("t_col", _vp), ("labels", _vp), ("params", _vp), ("grads", _vp),
     ]
 
 

@@ -14,6 +14,15 @@
 // whether the row holds its own id (self loop), and the effective neighbour
 // count (the divisor of MEAN): deg minus the self entries without gcn, deg
 // plus one when gcn has to add the missing self.
+//
+// The backward of "destination v reads its sources" is "source u reads every
+// destination v whose effective neighbourhood holds u": full_plan_transpose
+// builds that CSR with a stable counting sort over the forward rows (so each
+// transposed row lists its destinations in ascending id order, an entry the
+// forward row repeats repeated here), under the forward's rules -- a row's own
+// id is dropped, and under gcn v is a destination of itself exactly once --
+// and plans it like a forward CSR, at a seg_len of its own.  Symmetry of the
+// input is never assumed.
 #include "full_plan.hpp"
 
 #include <algorithm>
@@ -68,6 +77,41 @@ FullPlan* full_plan_build(const int64_t* row_ptr, const int32_t* col, int64_t n,
     return p.release();
 }
 
+FullPlan* full_plan_transpose(const FullPlan& fwd, const int64_t* row_ptr, const int32_t* col, int64_t seg_len) {
+    GS_REQUIRE(!fwd.transposed, GS_EINVAL, "the plan is already a transposed one");
+    const int64_t n = fwd.n;
+    GS_REQUIRE(row_ptr && (col || fwd.n_entries == 0), GS_EINVAL, "NULL CSR");
+    GS_REQUIRE((n ? row_ptr[n] : 0) == fwd.n_entries, GS_EINVAL, "the CSR is not the plan's");
+    std::vector<int64_t> trp(n + 1, 0);
+    for (int64_t v = 0; v < n; ++v) {
+        for (int64_t t = row_ptr[v]; t < row_ptr[v + 1]; ++t) {
+            GS_REQUIRE(col[t] >= 0 && col[t] < n, GS_ERANGE, "column id out of range");
+            if (col[t] != v) ++trp[col[t] + 1];
+        }
+        if (fwd.gcn) ++trp[v + 1];
+    }
+    for (int64_t u = 0; u < n; ++u) trp[u + 1] += trp[u];
+    std::vector<int32_t> tcol(static_cast<size_t>(n ? trp[n] : 0));
+    std::vector<int64_t> fill(trp.begin(), trp.end() - 1);
+    for (int64_t v = 0; v < n; ++v) {  // ascending v: every transposed row ends up ascending
+        for (int64_t t = row_ptr[v]; t < row_ptr[v + 1]; ++t) {
+            const int32_t u = col[t];
+            if (u != v) tcol[fill[u]++] = static_cast<int32_t>(v);
+        }
+        // v's own entry: every smaller destination of v is already in place and every larger one comes later
+        if (fwd.gcn) tcol[fill[v]++] = static_cast<int32_t>(v);
+    }
+    std::unique_ptr<FullPlan> p(full_plan_build(trp.data(), tcol.data(), n, 0, seg_len));
+    p->gcn = fwd.gcn;
+    p->transposed = true;
+    p->cnt = fwd.cnt;
+    std::fill(p->self_loop.begin(), p->self_loop.end(), uint8_t(0));
+    p->empty_rows.clear();
+    p->t_row_ptr = std::move(trp);
+    p->t_col = std::move(tcol);
+    return p.release();
+}
+
 int64_t full_plan_empty_in(const FullPlan& p, int64_t row0, int64_t n_rows) {
     const auto lo = std::lower_bound(p.empty_rows.begin(), p.empty_rows.end(), row0);
     const auto hi = std::lower_bound(p.empty_rows.begin(), p.empty_rows.end(), row0 + n_rows);
@@ -83,6 +127,15 @@ int gs_full_plan_create(const int64_t* row_ptr, const int32_t* col, int64_t n_no
     GS_API_BEGIN
     GS_REQUIRE(out, GS_EINVAL, "NULL out");
     *out = reinterpret_cast<gs_full_plan*>(gs::full_plan_build(row_ptr, col, n_nodes, gcn, seg_len));
+    GS_API_END
+}
+
+int gs_full_plan_transpose(const gs_full_plan* plan, const int64_t* row_ptr, const int32_t* col, int64_t seg_len,
+                           gs_full_plan** out) {
+    GS_API_BEGIN
+    GS_REQUIRE(plan && out, GS_EINVAL, "NULL argument");
+    *out = reinterpret_cast<gs_full_plan*>(
+        gs::full_plan_transpose(*reinterpret_cast<const gs::FullPlan*>(plan), row_ptr, col, seg_len));
     GS_API_END
 }
 
@@ -115,6 +168,8 @@ const void* gs_full_plan_array(const gs_full_plan* plan, int32_t which) {
         case GS_FP_COUNT: return p.cnt.data();
         case GS_FP_SELF_LOOP: return p.self_loop.data();
         case GS_FP_EMPTY_ROWS: return p.empty_rows.data();
+        case GS_FP_T_ROW_PTR: return p.transposed ? p.t_row_ptr.data() : nullptr;
+        case GS_FP_T_COL: return p.transposed ? p.t_col.data() : nullptr;
         default: return nullptr;
     }
 }

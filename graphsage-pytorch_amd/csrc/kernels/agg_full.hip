@@ -20,45 +20,6 @@
 
 namespace gs {
 
-template <int VEC>
-__device__ __forceinline__ void part_store(float* p, const float (&v)[VEC]) {
-    if constexpr (VEC == 1) {
-        *p = v[0];
-    } else {
-#pragma unroll
-        for (int q = 0; q < VEC / 4; ++q)
-            reinterpret_cast<float4*>(p)[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-    }
-}
-
-template <int VEC>
-__device__ __forceinline__ void part_load(const float* p, float (&v)[VEC]) {
-    if constexpr (VEC == 1) {
-        v[0] = *p;
-    } else {
-#pragma unroll
-        for (int q = 0; q < VEC / 4; ++q) {
-            const float4 t = reinterpret_cast<const float4*>(p)[q];
-            v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
-        }
-    }
-}
-
-struct FullArgs {
-    int64_t ldx, ldo;
-    const int64_t* row_ptr;
-    const int* col;
-    const int* items;       // the window's first item
-    const int64_t* slot_ptr;
-    const int* split_rows;  // the window's first split row
-    const int* cnt;
-    const uint8_t* self_loop;
-    float* part;
-    int64_t slot0;          // slot_ptr[row0]: the window's partials start at part[0]
-    int64_t seg_len;        // clamped to 2^31 - 1
-    int F, n_items, n_split, row0, gcn;
-};
-
 template <int OP, typename T, int VEC, int G>
 __global__ __launch_bounds__(kBlock) void agg_full_kernel(const T* __restrict__ X, T* __restrict__ out, FullArgs a) {
     const int gl = threadIdx.x % G;

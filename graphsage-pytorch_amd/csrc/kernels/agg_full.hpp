@@ -6,11 +6,63 @@
 
 namespace gs {
 
+// fp32 partial rows of a split row's segments, and the kernels' arguments (agg_full.hip, agg_full_bwd.hip)
+template <int VEC>
+__device__ __forceinline__ void part_store(float* p, const float (&v)[VEC]) {
+    if constexpr (VEC == 1) {
+        *p = v[0];
+    } else {
+#pragma unroll
+        for (int q = 0; q < VEC / 4; ++q)
+            reinterpret_cast<float4*>(p)[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+    }
+}
+
+template <int VEC>
+__device__ __forceinline__ void part_load(const float* p, float (&v)[VEC]) {
+    if constexpr (VEC == 1) {
+        v[0] = *p;
+    } else {
+#pragma unroll
+        for (int q = 0; q < VEC / 4; ++q) {
+            const float4 t = reinterpret_cast<const float4*>(p)[q];
+            v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
+        }
+    }
+}
+
+struct FullArgs {
+    int64_t ldx, ldo;
+    const int64_t* row_ptr;
+    const int* col;
+    const int* items;       // the window's first item
+    const int64_t* slot_ptr;
+    const int* split_rows;  // the window's first split row
+    const int* cnt;
+    const uint8_t* self_loop;
+    float* part;
+    int64_t slot0;          // slot_ptr[row0]: the window's partials start at part[0]
+    int64_t seg_len;        // clamped to 2^31 - 1
+    int F, n_items, n_split, row0, gcn;
+};
+
+
 // Bytes of fp32 partials the window [row0, row0 + n_rows) needs at width F.
 int64_t agg_full_ws_need(const FullPlan& p, int64_t F, int64_t row0, int64_t n_rows);
 // gs_agg_full (its argument checks included; every check before the first launch).
 void agg_full_launch(const FullPlan& p, const gs_full_plan_dev& d, gs_agg op, gs_dtype dt, const void* X, int64_t ldx,
                      int64_t F, const int64_t* row_ptr, const int32_t* col, int64_t row0, int64_t n_rows, void* out,
                      int64_t ldo, void* ws, int64_t ws_bytes, hipStream_t st);
+// gs_agg_full_argmax / gs_agg_full_bwd (agg_full_bwd.hip; every check before the first launch)
+int64_t agg_full_argmax_ws_need(const FullPlan& p, int64_t F, int64_t row0, int64_t n_rows);
+void agg_full_argmax_launch(const FullPlan& p, const gs_full_plan_dev& d, gs_dtype dt, const void* X, int64_t ldx,
+                            int64_t F, const int64_t* row_ptr, const int32_t* col, int64_t row0, int64_t n_rows,
+                            void* out, int64_t ldo, int32_t* argmax, int64_t lda, void* ws, int64_t ws_bytes,
+                            hipStream_t st);
+int64_t agg_full_bwd_ws_need(const FullPlan& tp, int64_t F);
+void agg_full_bwd_launch(const FullPlan& tp, const gs_full_plan_dev& td, gs_agg op, int64_t F,
+                         const int64_t* t_row_ptr, const int32_t* t_col, const float* dA, const float* dSelf,
+                         int64_t ldd, const int32_t* argmax, int64_t lda, const float* Hprev, float* dH, int64_t ldh,
+                         void* ws, int64_t ws_bytes, hipStream_t st);
 
 }  // namespace gs

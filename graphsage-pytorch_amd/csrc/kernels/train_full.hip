@@ -1,0 +1,227 @@
+// One full-batch training step over full neighbourhoods: the layer-wise
+// forward of infer_full.hip with every A_l and H_l kept (no ping-pong, no row
+// chunks: the backward reads them all), the loss head on the rows `nodes`, and
+// the backward -- dW_l from [H_{l-1} | A_l], [dSelf | dA] = dH_l W_l, and
+// dH_{l-1} from the backward aggregate (agg_full_bwd.hip) with the self-row
+// gradient and the relu mask of H_{l-1} folded into its epilogue.  Every
+// launch goes to the caller's stream and nothing is allocated: all buffers
+// live in the caller's workspace (layout_of).
+//
+// Row counts: the weight-gradient launcher cuts N rows into slabs of at most
+// 2048 rows (dw_rows_per_split) summed in slab order, its and the
+// input-gradient launcher's row offsets are 64-bit and their grids
+// ceil(N / 16) x tiles, so both take all N < 2^31 rows in one call; the
+// slab workspace is sized here by gs_sage_linear_bwd_weight_ws.
+#include "agg_full.hpp"
+#include "internal.hpp"
+
+#include <algorithm>
+
+namespace gs {
+
+namespace {
+
+constexpr int64_t kAlign = 256;
+int64_t round_up(int64_t b) { return (b + kAlign - 1) / kAlign * kAlign; }
+
+struct TrainLayout {
+    int64_t w1lp = -1;
+    int64_t a[GS_MAX_HOPS], h[GS_MAX_HOPS], am[GS_MAX_HOPS];  // A_l, H_l, argmax_l at index l - 1
+    int64_t dh[2] = {0, 0}, dself = -1, da = 0, e = 0, de = 0, cls = 0, slab = 0, part = 0;
+    int64_t slab_bytes = 0, part_bytes = 0, total = 0;
+};
+
+int64_t in_width(const gs_train_full_config& c, int l) {  // one concat half of layer l's input
+    return l == 1 ? c.feat_dim : c.hidden;
+}
+
+void check_config(const FullPlan& p, const FullPlan& tp, const gs_train_full_config& c) {
+    GS_REQUIRE(c.n_layers >= 1 && c.n_layers <= GS_MAX_HOPS, GS_EINVAL, "1 to 8 layers");
+    GS_REQUIRE(c.hidden >= 16 && c.hidden <= 256 && c.hidden % 16 == 0, GS_EINVAL,
+               "hidden must be a multiple of 16 in [16, 256]");
+    GS_REQUIRE(c.agg == GS_AGG_MEAN || c.agg == GS_AGG_MAX, GS_EINVAL, "agg_func must be MEAN or MAX");
+    GS_REQUIRE(c.feat_dtype == GS_F32 || c.feat_dtype == GS_BF16, GS_EINVAL, "dtype must be f32 or bf16");
+    GS_REQUIRE(c.feat_dim >= 1 && c.feat_dim < (1 << 28) && c.feat_ld >= c.feat_dim, GS_EINVAL, "bad feature shape");
+    GS_REQUIRE(c.n_classes >= 1 && c.n_classes + c.hidden < 16384, GS_EINVAL, "bad class count");
+    GS_REQUIRE(p.n >= 1, GS_EINVAL, "empty graph");
+    GS_REQUIRE(!p.transposed && tp.transposed && tp.n == p.n && tp.gcn == p.gcn, GS_EINVAL,
+               "tplan must be the forward plan's transpose");
+    GS_REQUIRE(c.max_nodes >= 1 && c.max_nodes <= p.n, GS_EINVAL, "max_nodes outside [1, n_nodes]");
+}
+
+TrainLayout layout_of(const FullPlan& p, const FullPlan& tp, const gs_train_full_config& c) {
+    check_config(p, tp, c);
+    TrainLayout lo;
+    const int64_t n = p.n, H = c.hidden, F = c.feat_dim, L = c.n_layers;
+    const int64_t es = c.feat_dtype == GS_BF16 ? 2 : 4;
+    const int64_t m = p.gcn ? 1 : 2;
+    int64_t off = 0;
+    auto take = [&](int64_t bytes) {
+        const int64_t at = off;
+        off += round_up(bytes);
+        return at;
+    };
+    if (c.feat_dtype == GS_BF16) lo.w1lp = take(H * m * F * 2);
+    for (int l = 1; l <= L; ++l) {
+        lo.a[l - 1] = take(n * (l == 1 ? F * es : H * 4));
+        lo.h[l - 1] = take(n * H * 4);
+        lo.am[l - 1] = (c.agg == GS_AGG_MAX && l >= 2) ? take(n * H * 4) : -1;
+    }
+    lo.dh[0] = take(n * H * 4);
+    if (L >= 2) {
+        lo.dh[1] = take(n * H * 4);
+        if (!p.gcn) lo.dself = take(n * H * 4);
+        lo.da = take(n * H * 4);
+    }
+    lo.e = take(c.max_nodes * H * 4);
+    lo.de = take(c.max_nodes * H * 4);
+    lo.cls = take(gs_cls_nll_ws_floats(c.max_nodes, H, c.n_classes) * 4);
+    for (int l = 1; l <= L; ++l)
+        lo.slab_bytes = std::max(lo.slab_bytes, gs_sage_linear_bwd_weight_ws(n, m * in_width(c, l), H));
+    lo.slab = take(lo.slab_bytes);
+    const int64_t fslots = p.slot_ptr[n], tslots = tp.slot_ptr[n];
+    lo.part_bytes = std::max(fslots * std::max(F, L >= 2 ? H : int64_t(0)) * 4 * (c.agg == GS_AGG_MAX ? 2 : 1),
+                             L >= 2 ? tslots * H * 4 : int64_t(0));
+    lo.part = take(lo.part_bytes);
+    lo.total = off;
+    return lo;
+}
+
+// E[i] = Hs[nodes[i]] (scatter: Hs[nodes[i]] = E[i]); H % 4 == 0, 16-byte aligned rows.
+template <bool SCATTER>
+__global__ __launch_bounds__(256) void rows_by_id_kernel(float* __restrict__ Hs, float* __restrict__ E,
+                                                         const int* __restrict__ nodes, int64_t B, int q) {
+    const int64_t t = blockIdx.x * int64_t(256) + threadIdx.x;
+    if (t >= B * q) return;
+    const int64_t i = t / q;
+    const int c = static_cast<int>(t % q);
+    float4* hs = reinterpret_cast<float4*>(Hs) + static_cast<int64_t>(nodes[i]) * q + c;
+    float4* e = reinterpret_cast<float4*>(E) + t;
+    if (SCATTER) *hs = *e;
+    else *e = *hs;
+}
+
+void ok(int rc) {
+    if (rc != GS_OK) fail(rc, gs_last_error());
+}
+
+}  // namespace
+
+void train_full_run(const FullPlan& p, const gs_full_plan_dev& d, const FullPlan& tp, const gs_full_plan_dev& td,
+                    const gs_train_full_config& c, const int32_t* nodes, int64_t B, int reuse_agg1, int stages,
+                    float* loss, void* ws, int64_t ws_bytes, hipStream_t st) {
+    const TrainLayout lo = layout_of(p, tp, c);
+    const int64_t n = p.n, H = c.hidden, L = c.n_layers, C = c.n_classes, m = p.gcn ? 1 : 2;
+    GS_REQUIRE(c.X && c.row_ptr && c.col && c.t_row_ptr && c.t_col && c.labels && c.params && c.grads && loss,
+               GS_EINVAL, "NULL pointer");
+    GS_REQUIRE(nodes && B >= 1 && B <= c.max_nodes, GS_EINVAL, "nodes: 1 to max_nodes ids");
+    GS_REQUIRE(stages >= 1 && stages <= GS_TF_ALL, GS_EINVAL, "bad stages");
+    GS_REQUIRE(ws && ws_bytes >= lo.total && (reinterpret_cast<uintptr_t>(ws) & (kAlign - 1)) == 0, GS_EINVAL,
+               "workspace smaller than gs_train_full_ws_bytes or not 256-byte aligned");
+    GS_REQUIRE(aligned16(c.params) && aligned16(c.grads), GS_EINVAL, "params / grads must be 16-byte aligned");
+    if (!p.empty_rows.empty())
+        fail(GS_EEMPTY, "gs_train_full: a node's effective neighbourhood is empty (reference: models.py:313, :321-325)");
+    char* base = static_cast<char*>(ws);
+    const gs_agg op = static_cast<gs_agg>(c.agg);
+    auto fptr = [&](int64_t o) { return reinterpret_cast<float*>(base + o); };
+    // the flat parameter layout: W_1 .. W_L, Wc, bc
+    int64_t woff[GS_MAX_HOPS + 1];
+    woff[0] = 0;
+    for (int l = 1; l <= L; ++l) woff[l] = woff[l - 1] + H * m * in_width(c, l);
+    const int64_t wc_off = woff[L], bc_off = wc_off + C * H;
+
+    if (stages & GS_TF_FORWARD) {
+        if (lo.w1lp >= 0) ok(gs_cast_f32_bf16(c.params, base + lo.w1lp, H * m * c.feat_dim, st));
+        for (int l = 1; l <= L; ++l) {
+            const gs_dtype dt = l == 1 ? static_cast<gs_dtype>(c.feat_dtype) : GS_F32;
+            const char* in = l == 1 ? static_cast<const char*>(c.X) : base + lo.h[l - 2];
+            const int64_t ldin = l == 1 ? c.feat_ld : H, fin = in_width(c, l);
+            if (lo.am[l - 1] >= 0)
+                agg_full_argmax_launch(p, d, dt, in, ldin, fin, c.row_ptr, c.col, 0, n, base + lo.a[l - 1], fin,
+                                       reinterpret_cast<int32_t*>(base + lo.am[l - 1]), fin, base + lo.part,
+                                       lo.part_bytes, st);
+            else if (l > 1 || !reuse_agg1)
+                agg_full_launch(p, d, op, dt, in, ldin, fin, c.row_ptr, c.col, 0, n, base + lo.a[l - 1], fin,
+                                base + lo.part, lo.part_bytes, st);
+            const void* W = (l == 1 && lo.w1lp >= 0) ? static_cast<const void*>(base + lo.w1lp)
+                                                     : static_cast<const void*>(c.params + woff[l - 1]);
+            linear_fwd_launch(dt, n, fin, H, p.gcn ? nullptr : in, ldin, nullptr, base + lo.a[l - 1], fin, W,
+                              fptr(lo.h[l - 1]), H, 1, st);
+        }
+    }
+    float* dh_top = fptr(lo.dh[(L - 1) % 2]);
+    if (stages & GS_TF_HEAD) {
+        const int q = static_cast<int>(H / 4);
+        const unsigned grid = static_cast<unsigned>((B * q + 255) / 256);
+        rows_by_id_kernel<false><<<dim3(grid), 256, 0, st>>>(fptr(lo.h[L - 1]), fptr(lo.e), nodes, B, q);
+        check_launch("gs_train_full(gather)");
+        // dE masked by relu'(H_L): the rows of dZ_L, every other row of it zero
+        ok(gs_cls_nll_fwd_bwd(B, H, C, fptr(lo.e), c.params + wc_off, c.params + bc_off, c.labels, nodes, 1, loss,
+                              fptr(lo.de), c.grads + wc_off, c.grads + bc_off, fptr(lo.cls), st));
+        GS_REQUIRE(hipMemsetAsync(dh_top, 0, n * H * 4, st) == hipSuccess, GS_EHIP, "memset failed");
+        rows_by_id_kernel<true><<<dim3(grid), 256, 0, st>>>(dh_top, fptr(lo.de), nodes, B, q);
+        check_launch("gs_train_full(scatter)");
+    }
+    if (stages & GS_TF_BACKWARD) {
+        for (int l = static_cast<int>(L); l >= 1; --l) {
+            const gs_dtype dt = l == 1 ? static_cast<gs_dtype>(c.feat_dtype) : GS_F32;
+            const char* in = l == 1 ? static_cast<const char*>(c.X) : base + lo.h[l - 2];
+            const int64_t ldin = l == 1 ? c.feat_ld : H, fin = in_width(c, l);
+            const float* dz = fptr(lo.dh[(l - 1) % 2]);  // dH_l, already masked by relu'(H_l)
+            float* dW = c.grads + woff[l - 1];
+            // gs_sage_linear_bwd_weight's two launches: row slabs, then their sum in slab order
+            const int S = linear_dw_slabs(dt, n, fin, H, p.gcn ? nullptr : in, ldin, nullptr, base + lo.a[l - 1], fin,
+                                          dz, nullptr, H, 0, dW, base + lo.slab, lo.slab_bytes, st, -1,
+                                          n >= 512 ? kDw1Phases : 1);
+            if (S > 1) sum_slabs_launch(fptr(lo.slab), S, H * m * fin, dW, nullptr, st);
+            if (l == 1) break;  // the feature table has no gradient
+            float* dself = p.gcn ? nullptr : fptr(lo.dself);
+            ok(gs_sage_linear_bwd_input(n, H, H, dz, nullptr, H, 0, c.params + woff[l - 1], dself, fptr(lo.da), H, st));
+            agg_full_bwd_launch(tp, td, op, H, c.t_row_ptr, c.t_col, fptr(lo.da), dself, H,
+                                lo.am[l - 1] >= 0 ? reinterpret_cast<const int32_t*>(base + lo.am[l - 1]) : nullptr, H,
+                                fptr(lo.h[l - 2]), fptr(lo.dh[(l - 2) % 2]), H, base + lo.part, lo.part_bytes, st);
+        }
+    }
+}
+
+}  // namespace gs
+
+extern "C" {
+
+int64_t gs_train_full_ws_bytes(const gs_full_plan* plan, const gs_full_plan* tplan, const gs_train_full_config* cfg) {
+    try {
+        if (!plan || !tplan || !cfg) return -1;
+        return gs::layout_of(*reinterpret_cast<const gs::FullPlan*>(plan),
+                             *reinterpret_cast<const gs::FullPlan*>(tplan), *cfg).total;
+    } catch (const std::exception& e) {
+        gs::set_error(e.what());
+        return -1;
+    }
+}
+
+int64_t gs_train_full_ws_offset(const gs_full_plan* plan, const gs_full_plan* tplan, const gs_train_full_config* cfg,
+                                int32_t which, int32_t layer) {
+    try {
+        if (!plan || !tplan || !cfg || layer < 1 || layer > cfg->n_layers || which < 0 || which > 1) return -1;
+        const gs::TrainLayout lo = gs::layout_of(*reinterpret_cast<const gs::FullPlan*>(plan),
+                                                 *reinterpret_cast<const gs::FullPlan*>(tplan), *cfg);
+        return which == 0 ? lo.h[layer - 1] : lo.a[layer - 1];
+    } catch (const std::exception& e) {
+        gs::set_error(e.what());
+        return -1;
+    }
+}
+
+int gs_train_full_forward_backward(const gs_full_plan* plan, const gs_full_plan_dev* dev, const gs_full_plan* tplan,
+                                   const gs_full_plan_dev* tdev, const gs_train_full_config* cfg, const int32_t* nodes,
+                                   int64_t n_nodes, int32_t reuse_agg1, int32_t stages, float* loss, void* ws,
+                                   int64_t ws_bytes, void* stream) {
+    GS_API_BEGIN
+    GS_REQUIRE(plan && dev && tplan && tdev && cfg, GS_EINVAL, "NULL argument");
+    gs::train_full_run(*reinterpret_cast<const gs::FullPlan*>(plan), *dev,
+                       *reinterpret_cast<const gs::FullPlan*>(tplan), *tdev, *cfg, nodes, n_nodes, reuse_agg1, stages,
+                       loss, ws, ws_bytes, gs::as_stream(stream));
+    GS_API_END
+}
+
+}  // extern "C"

@@ -61,6 +61,11 @@ def agg_fwd(agg_func, X, ptr_, idx, out, *, row_ptr=None, col=None, dst_ids=None
 # were slower, larger graphs keep the chunk buffer at this size).
 FULL_SEG_LEN = 256
 FULL_CHUNK_ROWS = 1 << 21
+# seg_len of the backward aggregate's transposed plan, the fastest measured on rmat2m at width 128
+# (profiles/full_train_bench.json, DESIGN §4 "Exact full-batch training"): the MEAN backward pays a division
+# per element and wants more items per hub row than the forward (5.0 ms at 64 against 6.4 at 256); the MAX
+# backward is flat from 64 to 256 (5.15-5.27 ms).
+FULL_BWD_SEG_LEN = 64
 
 
 class FullPlan:
@@ -72,12 +77,15 @@ class FullPlan:
 
     _DTYPES = {_lib.GS_FP_ITEMS: "int32", _lib.GS_FP_ITEM_PTR: "int64", _lib.GS_FP_SLOT_PTR: "int64",
                _lib.GS_FP_SPLIT_PTR: "int64", _lib.GS_FP_SPLIT_ROWS: "int32", _lib.GS_FP_COUNT: "int32",
-               _lib.GS_FP_SELF_LOOP: "uint8", _lib.GS_FP_EMPTY_ROWS: "int32"}
+               _lib.GS_FP_SELF_LOOP: "uint8", _lib.GS_FP_EMPTY_ROWS: "int32", _lib.GS_FP_T_ROW_PTR: "int64",
+               _lib.GS_FP_T_COL: "int32"}
+    is_transposed = False
 
     def __init__(self, graph, gcn=False, seg_len=None):
         import ctypes
 
         import numpy as np
+        self._t = {}
         if isinstance(graph, tuple):
             row_ptr, col = graph
             self.graph = None
@@ -94,6 +102,11 @@ class FullPlan:
         check(lib().gs_full_plan_create(ptr(self.row_ptr), ptr(self.col), len(self.row_ptr) - 1, int(bool(gcn)),
                                         seg_len, ctypes.byref(h)))
         self._h = h
+        self._read_dims()
+
+    def _read_dims(self):
+        import numpy as np
+        h = self._h
         dims = np.zeros(_lib.GS_FP_NDIMS, np.int64)
         check(lib().gs_full_plan_dims(h, ptr(dims)))
         self.n_nodes, self.n_items, self.n_slots, self.n_split, self.n_empty, self.seg_len = \
@@ -103,6 +116,29 @@ class FullPlan:
         self.n_entries = int(dims[_lib.GS_FP_N_ENTRIES])
         self._dev = {}
 
+    def transposed(self, seg_len=None):
+        """The plan of agg_full_bwd (gs_full_plan_transpose), built once per
+        seg_len (None: this plan's; <= 0: no row is split): a FullPlan over the
+        transposed CSR -- row u lists the destinations whose effective
+        neighbourhood (this plan's gcn rule) holds u, ascending -- cut into
+        segments of its own.  Its row_ptr / col are that CSR, and its
+        COUNT array is this plan's (the MEAN divisor of every destination).
+        Correct for directed input: symmetry is never assumed."""
+        import ctypes
+        if self.is_transposed:
+            raise ValueError("FullPlan.transposed: the plan is already a transposed one")
+        seg_len = self.seg_len if seg_len is None else int(seg_len)
+        if seg_len not in self._t:
+            h = ctypes.c_void_p()
+            check(lib().gs_full_plan_transpose(self._h, ptr(self.row_ptr), ptr(self.col), seg_len, ctypes.byref(h)))
+            t = FullPlan.__new__(FullPlan)
+            t._h, t._t, t.graph, t.is_transposed = h, {}, None, True
+            t._read_dims()
+            t.row_ptr = t.array(_lib.GS_FP_T_ROW_PTR)
+            t.col = t.array(_lib.GS_FP_T_COL)
+            self._t[seg_len] = t
+        return self._t[seg_len]
+
     def array(self, which):
         """A copy of one of the plan's host arrays (a _lib.GS_FP_* array id)."""
         import ctypes
@@ -111,11 +147,14 @@ class FullPlan:
         n = {_lib.GS_FP_ITEMS: 2 * self.n_items, _lib.GS_FP_ITEM_PTR: self.n_nodes + 1,
              _lib.GS_FP_SLOT_PTR: self.n_nodes + 1, _lib.GS_FP_SPLIT_PTR: self.n_nodes + 1,
              _lib.GS_FP_SPLIT_ROWS: self.n_split, _lib.GS_FP_COUNT: self.n_nodes,
-             _lib.GS_FP_SELF_LOOP: self.n_nodes, _lib.GS_FP_EMPTY_ROWS: self.n_empty}[which]
+             _lib.GS_FP_SELF_LOOP: self.n_nodes, _lib.GS_FP_EMPTY_ROWS: self.n_empty,
+             _lib.GS_FP_T_ROW_PTR: self.n_nodes + 1, _lib.GS_FP_T_COL: self.n_entries}[which]
         dt = np.dtype(self._DTYPES[which])
         if n == 0:
             return np.zeros(0, dt)
         p = lib().gs_full_plan_array(self._h, which)
+        if not p:
+            raise ValueError("FullPlan.array: only a transposed plan owns a CSR")
         buf = (ctypes.c_char * (n * dt.itemsize)).from_address(p)
         a = np.frombuffer(buf, dtype=dt).copy()
         return a.reshape(-1, 2) if which == _lib.GS_FP_ITEMS else a
@@ -151,7 +190,7 @@ class FullPlan:
             self._h = None
 
 
-def agg_full(agg_func, X, graph, out=None, *, gcn=False, seg_len=None, row0=0, n_rows=None, ws=None):
+def agg_full(agg_func, X, graph, out=None, *, gcn=False, seg_len=None, row0=0, n_rows=None, ws=None, argmax=None):
     """Full-neighbourhood mean/max of rows of X over the device CSR for the
     destination rows [row0, row0 + n_rows) (gs_agg_full): adj[v] without v, or
     with v exactly once under gcn; rows longer than `seg_len` entries are
@@ -159,18 +198,26 @@ def agg_full(agg_func, X, graph, out=None, *, gcn=False, seg_len=None, row0=0, n
     CSRGraph (its plan for (gcn, seg_len) is built once and kept on it) or a
     FullPlan, whose own gcn and seg_len then hold.  out: [n_rows, F] in X's
     dtype.  MEAN of an empty neighbourhood is a NaN row; MAX over a window
-    that holds one raises IndexError before any launch."""
-    _dev(X, out, ws)
+    that holds one raises IndexError before any launch.  `argmax` (MAX over
+    fp32 rows only; an int32 [n_rows, F] tensor): also filled with the id of
+    each element's first maximal source in the kernel's visiting order (CSR
+    row order, gcn's missing self row last), which agg_full_bwd routes the
+    gradient to; `out` is bitwise the same with and without it."""
+    _dev(X, out, ws, argmax)
     import ctypes
     plan = graph if isinstance(graph, FullPlan) else agg_full_plan(graph, gcn=gcn, seg_len=seg_len)
     if X.dtype not in _DT:
         raise TypeError("X must be float32 or bfloat16")
+    if argmax is not None and (agg_op(agg_func) != _lib.GS_AGG_MAX or X.dtype != torch.float32):
+        raise ValueError("agg_full: argmax is recorded for MAX over float32 rows only "
+                         "(a bf16 feature table's aggregate has no backward)")
     if X.dim() != 2 or X.stride(1) != 1 or X.shape[0] < plan.n_nodes:
         raise ValueError("X must be [n_nodes, F] with unit column stride")
     n_rows = plan.n_nodes - row0 if n_rows is None else int(n_rows)
     row0 = int(row0)
     F = X.shape[1]
-    need = int(lib().gs_agg_full_ws_bytes(plan.handle, F, row0, n_rows))
+    ws_fn = lib().gs_agg_full_ws_bytes if argmax is None else lib().gs_agg_full_argmax_ws_bytes
+    need = int(ws_fn(plan.handle, F, row0, n_rows))
     if need < 0:
         check(_lib.GS_EINVAL)
     if out is None:
@@ -180,6 +227,14 @@ def agg_full(agg_func, X, graph, out=None, *, gcn=False, seg_len=None, row0=0, n
     if ws is None:
         ws = torch.empty(max(need, 16), dtype=torch.uint8, device=X.device)
     d, rp, cl = plan.device(X.device)
+    if argmax is not None:
+        if argmax.dtype != torch.int32 or argmax.dim() != 2 or argmax.stride(1) != 1 or argmax.shape[0] < n_rows or \
+                argmax.shape[1] < F:
+            raise ValueError("argmax must be int32 [n_rows, F]")
+        check(lib().gs_agg_full_argmax(plan.handle, ctypes.byref(d), _DT[X.dtype], ptr(X), X.stride(0), F, ptr(rp),
+                                       ptr(cl), row0, n_rows, ptr(out), out.stride(0), ptr(argmax), argmax.stride(0),
+                                       ptr(ws), ws.numel() * ws.element_size(), _stream(X)))
+        return out
     check(lib().gs_agg_full(plan.handle, ctypes.byref(d), agg_op(agg_func), _DT[X.dtype], ptr(X), X.stride(0), F,
                             ptr(rp), ptr(cl), row0, n_rows, ptr(out), out.stride(0), ptr(ws),
                             ws.numel() * ws.element_size(), _stream(X)))
@@ -193,6 +248,57 @@ def agg_full_plan(graph, *, gcn=False, seg_len=None):
     if key not in plans:
         plans[key] = FullPlan(graph, gcn=key[0], seg_len=key[1])
     return plans[key]
+
+
+def agg_full_bwd_plan(graph, *, gcn=False, seg_len=None):
+    """The transposed FullPlan of a CSRGraph for (gcn, seg_len) (seg_len None:
+    FULL_BWD_SEG_LEN), built once per graph and kept on its forward plan."""
+    seg_len = FULL_BWD_SEG_LEN if seg_len is None else int(seg_len)
+    return agg_full_plan(graph, gcn=gcn).transposed(seg_len)
+
+
+def agg_full_bwd(agg_func, dA, graph, dH=None, *, gcn=False, seg_len=None, dSelf=None, argmax=None, Hprev=None,
+                 ws=None):
+    """Backward of agg_full over all rows (gs_agg_full_bwd), fp32:
+    dH[u] = sum over the destinations v that read u of dA[v] / count[v] (MEAN)
+    or of dA[v] where argmax[v] == u (MAX; `argmax` from agg_full), plus
+    dSelf[u], zeroed where Hprev[u] <= 0 (both optional).  `graph` is a
+    CSRGraph (its transposed plan for (gcn, seg_len) is built once and kept)
+    or a FullPlan, forward or transposed.  No atomics: bitwise repeatable."""
+    _dev(dA, dH, dSelf, argmax, Hprev, ws)
+    import ctypes
+    if isinstance(graph, FullPlan):
+        tplan = graph if graph.is_transposed else graph.transposed()
+    else:
+        tplan = agg_full_bwd_plan(graph, gcn=gcn, seg_len=seg_len)
+    op = agg_op(agg_func)
+    n = tplan.n_nodes
+    if dA.dtype != torch.float32 or dA.dim() != 2 or dA.stride(1) != 1 or dA.shape[0] != n:
+        raise ValueError("dA must be float32 [n_nodes, F] with unit column stride")
+    F = dA.shape[1]
+    if dH is None:
+        dH = torch.empty(n, F, dtype=torch.float32, device=dA.device)
+    for name, t, like in (("dH", dH, None), ("dSelf", dSelf, dA), ("Hprev", Hprev, dH)):
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != n or t.shape[1] < F:
+            raise ValueError(f"{name} must be float32 [n_nodes, F] with unit column stride")
+        if like is not None and t.stride(0) != like.stride(0):
+            raise ValueError(f"{name} must share its leading dimension with {'dA' if like is dA else 'dH'}")
+    if op == _lib.GS_AGG_MAX:
+        if argmax is None or argmax.dtype != torch.int32 or argmax.dim() != 2 or argmax.stride(1) != 1 or \
+                argmax.shape[0] != n or argmax.shape[1] < F:
+            raise ValueError("MAX needs the forward's argmax: int32 [n_nodes, F]")
+    need = int(lib().gs_agg_full_bwd_ws_bytes(tplan.handle, F))
+    if need < 0:
+        check(_lib.GS_EINVAL)
+    if ws is None:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dA.device)
+    d, rp, cl = tplan.device(dA.device)
+    check(lib().gs_agg_full_bwd(tplan.handle, ctypes.byref(d), op, F, ptr(rp), ptr(cl), ptr(dA), ptr(dSelf),
+                                dA.stride(0), ptr(argmax), argmax.stride(0) if argmax is not None else 0, ptr(Hprev),
+                                ptr(dH), dH.stride(0), ptr(ws), ws.numel() * ws.element_size(), _stream(dA)))
+    return dH
 
 
 def sage_linear_fwd(A, Wd, out, *, Xs=None, sidx=None, relu=True):

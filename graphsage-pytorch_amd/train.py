@@ -667,3 +667,234 @@ class FullEmbedder:
             return out
         idx = torch.from_numpy(np.ascontiguousarray(nodes, dtype=np.int64).reshape(-1)).to(self.device)
         return out.index_select(0, idx)
+
+
+# ------------------------------------------------------- full-batch training
+class FullTrainer:
+    """Exact full-batch training over full neighbourhoods: the reference's
+    num_sample=None branch (models.py:280-289) put through loss.backward(),
+    layer by layer over the device CSR for all N nodes (gs_train_full_*) --
+    no sampler, no pack and no `random` stream, bitwise repeatable.
+
+    One step: A_l = agg_full(H_{l-1}) and H_l = relu(W_l [H_{l-1} | A_l]) for
+    every node (H_L is bitwise FullEmbedder's), log_softmax + NLL mean over
+    the rows `nodes`, the backward through every layer (agg_full_bwd over the
+    transposed plan), then NativeTrainer's update: clip_grad_norm_(max_norm)
+    per model and SGD(lr), or `optimizer="adam"` (AdamW with `betas`, `eps`,
+    `weight_decay`).  The parameter layout, names and optimiser state are
+    NativeTrainer's, so a model moves between the two, FullEmbedder and the
+    GraphSage module through state_dict / weights.
+
+    bf16 features: layer 1 runs in bf16 (its aggregate rounded to bf16, W1
+    cast to bf16 each step), the layers above in fp32.  `cache_agg1`: layer
+    1's aggregate does not depend on the weights, so it is computed on the
+    first step and reused (the gradients are bitwise the same with it off);
+    call invalidate_cache() after changing the feature table in place.
+    `seg_len`: None takes the measured defaults, hip_ops.FULL_SEG_LEN for the
+    forward plan and FULL_BWD_SEG_LEN for the transposed one; a value holds
+    for both.
+
+    A node with an empty effective neighbourhood is refused here, at
+    construction (its NaN row would poison every loss): IndexError under MAX,
+    as FullEmbedder; ValueError under MEAN -- use gcn=True, or train on a
+    subgraph in which every node has a neighbour.
+
+    Memory: every A_l and H_l is kept for the backward.  With N nodes, F
+    features of e bytes (4, or 2 for bf16), H hidden, L layers, B = len(nodes)
+    and the split rows' partial slots S (S_t transposed), ws_bytes is about
+        N (F e + 4 H)                          A_1, H_1
+      + (L - 1) N 4 H (2, or 3 under MAX)      A_l, H_l (and argmax_l), l >= 2
+      + 4 N H (1 if L == 1 else 4, 3 with gcn) dH ping-pong, dSelf, dA
+      + ceil(N / 2048) 4 K H                   dW row slabs (K = the widest layer input)
+      + 4 max(S max(F, H), S_t H) + O(B H)     partials, loss head
+    -- about 12 N H bytes per layer above the first: 8.7 GB on a 2.1 M-node
+    graph at H = 128, L = 2, F = 128.  The graph's entry count enters only
+    through the plans and the two device CSRs (12 bytes per entry each).
+
+    Single GPU.  Out of scope: restricting the work to the L-hop receptive
+    field of `nodes` (every step computes all N rows), data parallel, and the
+    unsupervised losses."""
+
+    def __init__(self, graph, features, labels, n_classes, num_layers=2, hidden=128, agg_func="MEAN", gcn=False,
+                 lr=0.7, max_norm=5.0, seed=824, weights=None, optimizer="sgd", betas=(0.9, 0.999), eps=1e-8,
+                 weight_decay=0.0, seg_len=None, cache_agg1=True):
+        self.optimizer = optimizer
+        self._opt_kind = optimizer_kind(optimizer)
+        self.betas, self.eps, self.weight_decay = (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
+        self.agg, self.gcn, self.lr, self.max_norm = agg_func, bool(gcn), float(lr), float(max_norm)
+        op = ops.agg_op(agg_func)
+        self.plan = ops.agg_full_plan(graph, gcn=gcn, seg_len=seg_len)
+        if self.plan.n_empty:
+            if agg_func == "MAX":
+                raise IndexError(f"MAX aggregation over an empty neighbourhood ({self.plan.n_empty} nodes have none; "
+                                 "reference: models.py:321-325)")
+            raise ValueError(f"FullTrainer: {self.plan.n_empty} nodes have an empty neighbourhood, whose MEAN is a "
+                             "NaN row in every loss; use gcn=True or train on a self-contained subgraph")
+        if not features.is_cuda:
+            raise RuntimeError("FullTrainer runs on a HIP device")
+        if features.dim() != 2 or features.stride(1) != 1 or features.shape[0] != graph.n_nodes or \
+                features.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("features must be [n_nodes, F] fp32 or bf16 with unit column stride")
+        self.graph, self.X, self.device = graph, features, features.device
+        self.L, self.H, self.C, F = int(num_layers), int(hidden), int(n_classes), features.shape[1]
+        if labels.numel() != graph.n_nodes:
+            raise ValueError("labels must hold one class per node")
+        if weights is None:
+            weights = reference_init(self.L, F, self.H, self.C, gcn, seed)
+        sage_w, cls_w, cls_b = weights
+        m = 1 if gcn else 2
+        shapes = [(self.H, m * (F if l == 0 else self.H)) for l in range(self.L)] + [(self.C, self.H), (self.C,)]
+        tensors = list(sage_w) + [cls_w, cls_b]
+        if len(tensors) != len(shapes):
+            raise ValueError(f"weights: {self.L} SageLayer weights, the classifier's weight and its bias expected")
+        for i, (t, want) in enumerate(zip(tensors, shapes)):
+            if tuple(t.shape) != want:
+                raise ValueError(f"weights[{i}] must be {list(want)}, got {list(t.shape)}")
+        self.labels = labels.reshape(-1).to(device=self.device, dtype=torch.int32)
+        names = [f"sage_layer{i}.weight" for i in range(1, self.L + 1)] + ["layer.0.weight", "layer.0.bias"]
+        self.p = FlatParams(tensors, names, [0, self.L], self.device)
+        self.tplan = self.plan.transposed(ops.FULL_BWD_SEG_LEN if seg_len is None else seg_len)
+        self._dev, self.row_ptr, self.col = self.plan.device(self.device)
+        self._tdev, self.t_row_ptr, self.t_col = self.tplan.device(self.device)
+        self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self.clip_ws = torch.empty(65 * 2, dtype=torch.float32, device=self.device)
+        self.cfg = _lib.TrainFullConfig(
+            n_layers=self.L, hidden=self.H, n_classes=self.C, agg=op,
+            feat_dtype=_lib.GS_BF16 if features.dtype == torch.bfloat16 else _lib.GS_F32, feat_dim=F,
+            feat_ld=features.stride(0), max_nodes=graph.n_nodes, X=features.data_ptr(),
+            row_ptr=self.row_ptr.data_ptr(), col=self.col.data_ptr(), t_row_ptr=self.t_row_ptr.data_ptr(),
+            t_col=self.t_col.data_ptr(), labels=self.labels.data_ptr(), params=self.p.params.data_ptr(),
+            grads=self.p.grads.data_ptr())
+        need = int(lib().gs_train_full_ws_bytes(self.plan.handle, self.tplan.handle, ctypes.byref(self.cfg)))
+        if need < 0:
+            check(_lib.GS_EINVAL)
+        self.ws_bytes = need
+        self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+        self._ws_off = (-self._ws.data_ptr()) % 256
+        self.cache_agg1 = bool(cache_agg1)
+        self._agg1_valid = False
+        self._opt_step = 0
+        self.opt_m = self.opt_v = None
+        if self._opt_kind == _lib.GS_OPT_ADAM:
+            self.opt_m = torch.zeros_like(self.p.params)
+            self.opt_v = torch.zeros_like(self.p.params)
+        self._embedder = None
+
+    # -- parameters and optimiser state: NativeTrainer's names and layout
+    def state_dict(self):
+        return self.p.state_dict()
+
+    def load_state_dict(self, sd):
+        """Copy the named parameters of state_dict() back into the flat buffer."""
+        for i, n in enumerate(self.p.names):
+            self.p.view(i).copy_(sd[n])
+
+    def weights(self):
+        return [self.p.view(i) for i in range(self.L)]
+
+    def optimizer_state(self):
+        """{"step", "m", "v"}, as NativeTrainer.optimizer_state()."""
+        return {"step": self._opt_step,
+                "m": None if self.opt_m is None else self.opt_m.detach().clone(),
+                "v": None if self.opt_v is None else self.opt_v.detach().clone()}
+
+    def load_optimizer_state(self, state):
+        if self.opt_m is not None:
+            if state["m"] is None or state["v"] is None:
+                raise ValueError("load_optimizer_state: the state holds no Adam moments")
+            if state["m"].numel() != self.opt_m.numel() or state["v"].numel() != self.opt_v.numel():
+                raise ValueError("load_optimizer_state: moment size != parameter count")
+            self.opt_m.copy_(state["m"].reshape(-1))
+            self.opt_v.copy_(state["v"].reshape(-1))
+        self._opt_step = int(state["step"])
+
+    def invalidate_cache(self):
+        """Recompute layer 1's aggregate on the next step (the feature table changed in place)."""
+        self._agg1_valid = False
+
+    def _nodes(self, nodes):
+        """`nodes` as a device int32 vector of unique ids in [0, N); every check before any launch of the step."""
+        n = self.graph.n_nodes
+        if isinstance(nodes, torch.Tensor):
+            if not nodes.is_cuda:
+                raise RuntimeError("FullTrainer: nodes must be a device tensor (or a host array / list of ids)")
+            if nodes.dtype != torch.int32 or nodes.dim() != 1 or not nodes.is_contiguous():
+                raise TypeError("FullTrainer: nodes must be a contiguous 1-D int32 tensor")
+            if nodes.numel() < 1 or nodes.numel() > n:
+                raise ValueError("FullTrainer: nodes must hold 1 to n_nodes ids")
+            key = (nodes.data_ptr(), nodes.numel(), nodes._version)
+            if getattr(self, "_nodes_ok", None) != key:
+                lo, hi = int(nodes.min()), int(nodes.max())
+                if lo < 0 or hi >= n:
+                    raise IndexError("FullTrainer: node id out of range")
+                if int(torch.unique(nodes).numel()) != nodes.numel():
+                    raise ValueError("FullTrainer: duplicate ids in nodes")
+                self._nodes_ok = key
+            return nodes
+        a = np.asarray(nodes)
+        if a.ndim != 1 or a.size < 1 or a.dtype.kind not in "iu":
+            raise TypeError("FullTrainer: nodes must be a 1-D array of integer ids")
+        if a.min() < 0 or a.max() >= n:
+            raise IndexError("FullTrainer: node id out of range")
+        if len(np.unique(a)) != a.size:
+            raise ValueError("FullTrainer: duplicate ids in nodes")
+        return torch.from_numpy(a.astype(np.int32)).to(self.device)
+
+    def forward_backward(self, nodes, stages=_lib.GS_TF_ALL):
+        """Loss (device scalar, the NLL mean over `nodes`) and the raw,
+        unclipped gradients into self.p.grads: one native call that issues
+        every launch of the step on the current stream.  `nodes`: unique ids,
+        a device int32 vector or a host array.  `stages`: a _lib.GS_TF_* subset,
+        for measurement only."""
+        nodes = self._nodes(nodes)
+        reuse = self.cache_agg1 and self._agg1_valid
+        check(lib().gs_train_full_forward_backward(
+            self.plan.handle, ctypes.byref(self._dev), self.tplan.handle, ctypes.byref(self._tdev),
+            ctypes.byref(self.cfg), nodes.data_ptr(), nodes.numel(), int(reuse), int(stages), self.loss.data_ptr(),
+            self._ws.data_ptr() + self._ws_off, self.ws_bytes, _lib.stream_ptr(self.device)))
+        if stages & _lib.GS_TF_FORWARD:
+            self._agg1_valid = True
+        self._last_nodes = nodes  # alive until the stream has run the step
+        return self.loss
+
+    def apply_update(self):
+        """clip per model + SGD, or + AdamW (gs_clip_sgd / gs_clip_adam) on the flat buffers."""
+        self._opt_step += 1
+        if self._opt_kind == _lib.GS_OPT_ADAM:
+            ops.clip_adam(self.p.group_off, self.p.params, self.p.grads, self.opt_m, self.opt_v, 1.0, self.max_norm,
+                          self.lr, self.betas, self.eps, self.weight_decay, self._opt_step, self.clip_ws)
+        else:
+            ops.clip_sgd(self.p.group_off, self.p.params, self.p.grads, 1.0, self.max_norm, self.lr, self.clip_ws)
+
+    def step(self, nodes):
+        loss = self.forward_backward(nodes)
+        self.apply_update()
+        return loss
+
+    def hidden(self, layer=None, which=0):
+        """A view of H_layer (which=0) or A_layer (which=1) as the last
+        forward left it in the workspace ([N, width]; layer None: the last)."""
+        layer = self.L if layer is None else int(layer)
+        off = int(lib().gs_train_full_ws_offset(self.plan.handle, self.tplan.handle, ctypes.byref(self.cfg), which,
+                                                layer))
+        if off < 0:
+            check(_lib.GS_EINVAL)
+        n = self.graph.n_nodes
+        if which == 1 and layer == 1:
+            w, dt = self.X.shape[1], self.X.dtype
+        else:
+            w, dt = self.H, torch.float32
+        nbytes = n * w * (2 if dt == torch.bfloat16 else 4)
+        raw = self._ws[self._ws_off + off:self._ws_off + off + nbytes]
+        return raw.view(dt).view(n, w)
+
+    def embed(self, nodes=None):
+        """[N, hidden] exact embeddings under the current weights (or the rows
+        `nodes`): FullEmbedder over this trainer's parameter views, bitwise
+        FullEmbedder(graph, X, tr.weights(), ...).embed()."""
+        if self._embedder is None:
+            self._embedder = FullEmbedder(self.graph, self.X, self.weights(), agg_func=self.agg, gcn=self.gcn,
+                                          seg_len=self.plan.seg_len)
+        for dst, src in zip(self._embedder.W, self.weights()):
+            dst.copy_(src)
+        return self._embedder.embed(nodes)

@@ -802,7 +802,8 @@ void gs_runner_destroy(gs_runner* r);
 /* ------------------------------------- exact full-neighbourhood inference
  * The reference's num_sample=None branch (models.py:280-289) for every node,
  * layer by layer over the device CSR: H_1 for all N rows from X, H_2 from H_1,
- * ...  No sampler, no pack, no random stream.  Single GPU, inference only.
+ * ...  No sampler, no pack, no random stream.  Single GPU (training over the same
+ * forward: the next section).
  *
  * The plan (host, once per graph, gcn flag and seg_len): destination row v
  * becomes max(1, ceil(deg(v) / seg_len)) work items (v, s), item s covering
@@ -881,6 +882,99 @@ typedef struct {
 int64_t gs_infer_full_ws_bytes(const gs_full_plan* plan, const gs_infer_full_config* cfg);
 int gs_infer_full(const gs_full_plan* plan, const gs_full_plan_dev* dev, const gs_infer_full_config* cfg,
                   float* out, int64_t ldo, void* ws, int64_t ws_bytes, void* stream);
+
+/* ------------------------------------- exact full-neighbourhood training
+ * The backward of gs_agg_full and a driver that strings one full-batch step
+ * together from it and the existing SageLayer / loss-head launchers.
+ *
+ * The transposed plan (host): the CSR whose row u lists every destination v
+ * whose effective neighbourhood holds u, ascending (a stable counting sort; an
+ * entry the forward row repeats is repeated), under the forward plan's rules:
+ * a row's own id is dropped, and under gcn v is its own destination exactly
+ * once, self loop or not.  Nothing is assumed about symmetry.  The result is a
+ * plan of its own over that CSR (segments of seg_len; <= 0: no split) which also
+ * owns the CSR (arrays GS_FP_T_ROW_PTR int64 [n + 1] and GS_FP_T_COL int32
+ * [n_entries]; NULL for a forward plan); its COUNT array is the forward
+ * plan's, the MEAN divisor of each destination.  (row_ptr, col) must be the
+ * host CSR the forward plan was built from. */
+enum { GS_FP_T_ROW_PTR = 8, GS_FP_T_COL = 9 };
+int gs_full_plan_transpose(const gs_full_plan* plan, const int64_t* row_ptr, const int32_t* col,
+                           int64_t seg_len, gs_full_plan** out);
+
+/* gs_agg_full for MAX over fp32 rows (dt must be GS_F32: GS_EINVAL otherwise)
+ * that also records argmax[n_rows][F] (int32, row stride lda): the global id
+ * of the first maximal source in the order the kernel visits them -- CSR row
+ * order, the row's own id skipped (kept in place under gcn), gcn's missing
+ * self row last.  Partials carry their argmax and the combine pass folds them
+ * in segment order with a strict >, so first-wins survives segmentation.  out
+ * is bitwise gs_agg_full's.  ws: gs_agg_full_argmax_ws_bytes (twice
+ * gs_agg_full_ws_bytes: a value and an id per partial element). */
+int64_t gs_agg_full_argmax_ws_bytes(const gs_full_plan* plan, int64_t F, int64_t row0, int64_t n_rows);
+int gs_agg_full_argmax(const gs_full_plan* plan, const gs_full_plan_dev* dev, gs_dtype dt,
+                       const void* X, int64_t ldx, int64_t F, const int64_t* row_ptr, const int32_t* col,
+                       int64_t row0, int64_t n_rows, void* out, int64_t ldo, int32_t* argmax, int64_t lda,
+                       void* ws, int64_t ws_bytes, void* stream);
+
+/* Backward of gs_agg_full over all n rows, as a gather over the transposed
+ * plan `tplan` (tdev: its device arrays, count = the forward counts;
+ * t_row_ptr / t_col: its CSR on the device), fp32:
+ *   MEAN  g[u] = sum over v in T(u) of dA[v] / count[v]   (a true division per element)
+ *   MAX   g[u][f] = sum over distinct v in T(u) of dA[v][f] where argmax[v][f] == u
+ *   dH[u] = (g[u] + dSelf[u]) zeroed where Hprev[u] <= 0
+ * dSelf (row stride ldd, as dA) and Hprev (row stride ldh, as dH) may be NULL.
+ * One lane group per (source row, segment), partials for split rows in ws
+ * (gs_agg_full_bwd_ws_bytes) and a combine pass in segment order: no atomics,
+ * a pure function of the inputs and the transposed plan's seg_len. */
+int64_t gs_agg_full_bwd_ws_bytes(const gs_full_plan* tplan, int64_t F);
+int gs_agg_full_bwd(const gs_full_plan* tplan, const gs_full_plan_dev* tdev, gs_agg op, int64_t F,
+                    const int64_t* t_row_ptr, const int32_t* t_col, const float* dA, const float* dSelf,
+                    int64_t ldd, const int32_t* argmax, int64_t lda, const float* Hprev, float* dH,
+                    int64_t ldh, void* ws, int64_t ws_bytes, void* stream);
+
+/* One full-batch training step's forward, loss head and backward, every
+ * launch on the caller's stream, nothing allocated (ws: gs_train_full_ws_bytes
+ * bytes, 256-byte aligned, kept by the caller between steps):
+ *   forward  l = 1..L: A_l = gs_agg_full(H_{l-1}) (with argmax for MAX at l >= 2),
+ *            H_l = relu(W_l [H_{l-1} | A_l]) (relu(W_l A_l) under gcn); every A_l and
+ *            H_l is kept; H_L is bitwise gs_infer_full's.  bf16 features: layer 1's
+ *            aggregate and W_1 rounded to bf16, the layers above in fp32.
+ *   head     E = H_L[nodes] (n_nodes unique device ids), gs_cls_nll_fwd_bwd with
+ *            roots = nodes (loss = NLL mean over nodes), dE scattered into a zeroed dH_L.
+ *   backward l = L..1: dW_l, then for l >= 2 [dSelf | dA] = dH_l W_l and
+ *            dH_{l-1} = gs_agg_full_bwd(dA, dSelf, relu mask of H_{l-1}).
+ * params / grads: the flat fp32 layout [W_1 | .. | W_L | Wc | bc] (W_l
+ * [hidden][K_l], Wc [n_classes][hidden]); grads are overwritten, unclipped.
+ * reuse_agg1 != 0: A_1 in ws is still valid (same ws, features and graph as
+ * the call that wrote it) and is not recomputed; the results are bitwise the
+ * same either way.  stages: GS_TF_ALL, or a subset for measurement (a subset
+ * reads what an earlier full call left in ws). */
+typedef struct {
+    int32_t n_layers, hidden, n_classes;
+    int32_t agg;             /* gs_agg */
+    int32_t feat_dtype;      /* gs_dtype */
+    int32_t pad_;
+    int64_t feat_dim, feat_ld;
+    int64_t max_nodes;       /* capacity of the loss head (rows of `nodes`) */
+    const void* X;
+    const int64_t* row_ptr;  /* device CSR (forward) */
+    const int32_t* col;
+    const int64_t* t_row_ptr;/* device CSR of the transposed plan */
+    const int32_t* t_col;
+    const int32_t* labels;   /* [n] device */
+    const float* params;
+    float* grads;
+} gs_train_full_config;
+enum { GS_TF_FORWARD = 1, GS_TF_HEAD = 2, GS_TF_BACKWARD = 4, GS_TF_ALL = 7 };
+/* Byte offsets into ws of the kept activations (which: 0 = H_l, 1 = A_l; l = 1..L); -1 on error. */
+int64_t gs_train_full_ws_offset(const gs_full_plan* plan, const gs_full_plan* tplan,
+                                const gs_train_full_config* cfg, int32_t which, int32_t layer);
+int64_t gs_train_full_ws_bytes(const gs_full_plan* plan, const gs_full_plan* tplan,
+                               const gs_train_full_config* cfg);
+int gs_train_full_forward_backward(const gs_full_plan* plan, const gs_full_plan_dev* dev,
+                                   const gs_full_plan* tplan, const gs_full_plan_dev* tdev,
+                                   const gs_train_full_config* cfg, const int32_t* nodes, int64_t n_nodes,
+                                   int32_t reuse_agg1, int32_t stages, float* loss,
+                                   void* ws, int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

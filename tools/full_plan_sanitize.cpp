@@ -3,8 +3,9 @@
 // first and in later segments, rows of degree 0, 1, seg_len, seg_len + 1 and
 // 3 * seg_len + 5, an isolated last node and the highest id as a neighbour,
 // planned at several seg_len with gcn on and off; every plan is recounted
-// here (items cover each row once, in order; counts, flags, empty rows), and
-// the error paths are taken.
+// here (items cover each row once, in order; counts, flags, empty rows), its
+// transposed plan (gs_full_plan_transpose; the CSR is directed) is checked
+// entry by entry, and the error paths are taken.
 //   make -C graphsage-pytorch_amd/csrc sanitize-full-plan
 // builds it with the host sources under -fsanitize=address,undefined (the
 // Makefile's ASANFLAGS) and runs it once; it prints one line and exits 0.
@@ -109,6 +110,40 @@ int main() {
             CHECK(gcn ? n_empty == 0 : n_empty >= 2);  // the isolated node and the self-loop-only row
             items_total += it;
             ++plans;
+            // the transposed plan (gs_full_plan_transpose): every kept entry (v, u) of this directed CSR turns up
+            // once in row u, rows ascending, v itself exactly once under gcn; counts are the forward plan's
+            gs_full_plan* t = nullptr;
+            CHECK(gs_full_plan_transpose(p, row_ptr.data(), col.data(), seg_len, &t) == GS_OK);
+            int64_t tdims[GS_FP_NDIMS];
+            CHECK(gs_full_plan_dims(t, tdims) == GS_OK && tdims[GS_FP_N_NODES] == n && tdims[GS_FP_SEG_LEN] == sl);
+            const int64_t* trp = arr<int64_t>(t, GS_FP_T_ROW_PTR);
+            const int32_t* tcol = arr<int32_t>(t, GS_FP_T_COL);
+            const int32_t* tcnt = arr<int32_t>(t, GS_FP_COUNT);
+            const int64_t* titem_ptr = arr<int64_t>(t, GS_FP_ITEM_PTR);
+            CHECK(arr<int64_t>(p, GS_FP_T_ROW_PTR) == nullptr && arr<int32_t>(p, GS_FP_T_COL) == nullptr);
+            int64_t kept = 0;
+            for (int64_t v = 0; v < n; ++v) {
+                kept += gcn;
+                for (int32_t u : rows[v]) kept += u != v;
+                CHECK(tcnt[v] == cnt[v]);
+            }
+            CHECK(trp[0] == 0 && trp[n] == kept && tdims[GS_FP_N_ENTRIES] == kept && tdims[GS_FP_N_EMPTY] == 0);
+            for (int64_t u = 0; u < n; ++u) {
+                const int64_t deg = trp[u + 1] - trp[u];
+                CHECK(deg >= 0 && titem_ptr[u + 1] - titem_ptr[u] == (deg == 0 ? 1 : (deg - 1) / sl + 1));
+                int64_t own = 0;
+                for (int64_t e = trp[u]; e < trp[u + 1]; ++e) {
+                    const int32_t v = tcol[e];
+                    CHECK(v >= 0 && v < n && (e == trp[u] || tcol[e - 1] <= v));
+                    own += v == u;
+                    CHECK(v == u || std::find(rows[v].begin(), rows[v].end(), static_cast<int32_t>(u)) != rows[v].end());
+                }
+                CHECK(own == gcn);
+            }
+            gs_full_plan* tt = nullptr;
+            CHECK(gs_full_plan_transpose(t, trp, tcol, seg_len, &tt) == GS_EINVAL);  // already transposed
+            CHECK(gs_full_plan_transpose(p, row_ptr.data(), col.data(), seg_len, nullptr) == GS_EINVAL);
+            gs_full_plan_destroy(t);
             gs_full_plan_destroy(p);
         }
     // error paths: a column id out of range, a decreasing row pointer, NULL out
