@@ -200,6 +200,16 @@ _SIGS = {
     "gs_train_full_ws_offset": (_i64, [_vp, _vp, _vp, _i32, _i32]),
     "gs_train_full_ws_bytes": (_i64, [_vp, _vp, _vp]),
     "gs_train_full_forward_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),
+    "gs_full_field_bytes": (_i64, [_vp, _vp, _i32]),
+    "gs_full_field_offset": (_i64, [_vp, _vp, _i32, _i32, _i32]),
+    "gs_full_field_build": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "gs_full_field_counts": (_i32, [_vp, _vp, _vp, _vp]),
+    "gs_agg_full_field": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp,
+                                 _i64, _vp, _i64, _vp]),
+    "gs_agg_full_bwd_field": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
+                                     _i64, _vp, _i64, _vp, _i64, _vp]),
+    "gs_train_full_field_forward_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp,
+                                                    _i64, _vp]),
 }
 
 (GS_FP_N_NODES, GS_FP_N_ITEMS, GS_FP_N_SLOTS, GS_FP_N_SPLIT, GS_FP_N_EMPTY, GS_FP_SEG_LEN, GS_FP_GCN,
@@ -208,10 +218,17 @@ _SIGS = {
  GS_FP_EMPTY_ROWS) = range(8)
 GS_FP_T_ROW_PTR, GS_FP_T_COL = 8, 9  # a transposed plan's own CSR (gs_full_plan_transpose)
 GS_TF_FORWARD, GS_TF_HEAD, GS_TF_BACKWARD, GS_TF_ALL = 1, 2, 4, 7
+# a receptive field (gs_full_field_*): counts[l] = n_l, counts[GS_FF_LAYER0 + 4 (l - 1) + k] per layer
+GS_FF_LAYER0, GS_FF_NCOUNTS = GS_MAX_HOPS + 1, GS_MAX_HOPS + 1 + 4 * GS_MAX_HOPS
+GS_FF_ROWS, GS_FF_POS, GS_FF_ITEMS, GS_FF_SPLIT, GS_FF_T_ITEMS, GS_FF_T_SPLIT = range(6)
 
 
 class FullPlanDev(ctypes.Structure):
     _fields_ = [("items", _vp), ("slot_ptr", _vp), ("split_rows", _vp), ("count", _vp), ("self_loop", _vp)]
+
+
+class FullField(ctypes.Structure):
+    _fields_ = [("n_layers", _i32), ("pad_", _i32), ("buf", _vp), ("buf_bytes", _i64), ("counts", _i64 * GS_FF_NCOUNTS)]
 
 
 class InferFullConfig(ctypes.Structure):

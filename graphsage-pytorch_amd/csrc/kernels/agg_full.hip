@@ -13,6 +13,11 @@
 // divides by the plan's count.  No atomics: the result is a pure function of
 // the inputs and seg_len.  What a segment cannot see on its own -- whether the
 // row holds a self loop, and MEAN's divisor -- is read from the plan.
+//
+// MAP (a template parameter of both kernels): the rows of a receptive field
+// (full_field.hip).  The items and split rows are the field's, and a row is
+// written to row pos[v] of a compact output; the walk, the partial slots and
+// the combine order are the same, so a row is bitwise the unmapped one.
 #include "agg_dev.hpp"
 #include "agg_full.hpp"
 
@@ -20,7 +25,7 @@
 
 namespace gs {
 
-template <int OP, typename T, int VEC, int G>
+template <int OP, typename T, int VEC, int G, bool MAP>
 __global__ __launch_bounds__(kBlock) void agg_full_kernel(const T* __restrict__ X, T* __restrict__ out, FullArgs a) {
     const int gl = threadIdx.x % G;
     const int li = blockIdx.x * (kBlock / G) + threadIdx.x / G;
@@ -89,13 +94,13 @@ __global__ __launch_bounds__(kBlock) void agg_full_kernel(const T* __restrict__ 
 #pragma unroll
             for (int v = 0; v < VEC; ++v) acc[v] /= c;
         }
-        RowIO<T, VEC>::store(out + static_cast<int64_t>(node - a.row0) * a.ldo + f0, acc);
+        RowIO<T, VEC>::store(out + static_cast<int64_t>(MAP ? a.pos[node] : node - a.row0) * a.ldo + f0, acc);
     }
 }
 
 // One lane group per split row: its partials in segment order, four loads in
 // flight, then gcn's self row, the mean's division and the output row.
-template <int OP, typename T, int VEC, int G>
+template <int OP, typename T, int VEC, int G, bool MAP>
 __global__ __launch_bounds__(kBlock) void agg_full_combine_kernel(const T* __restrict__ X, T* __restrict__ out,
                                                                   FullArgs a) {
     constexpr int NP = 4;
@@ -143,17 +148,21 @@ __global__ __launch_bounds__(kBlock) void agg_full_combine_kernel(const T* __res
 #pragma unroll
             for (int v = 0; v < VEC; ++v) acc[v] /= c;
         }
-        RowIO<T, VEC>::store(out + static_cast<int64_t>(node - a.row0) * a.ldo + f0, acc);
+        RowIO<T, VEC>::store(out + static_cast<int64_t>(MAP ? a.pos[node] : node - a.row0) * a.ldo + f0, acc);
     }
 }
 
 template <int OP, typename T, int VEC, int G>
 static void launch_full(const T* X, T* out, const FullArgs& a, hipStream_t st) {
     constexpr int per = kBlock / G;
-    if (a.n_items > 0)
-        agg_full_kernel<OP, T, VEC, G><<<dim3((a.n_items + per - 1) / per), kBlock, 0, st>>>(X, out, a);
-    if (a.n_split > 0)
-        agg_full_combine_kernel<OP, T, VEC, G><<<dim3((a.n_split + per - 1) / per), kBlock, 0, st>>>(X, out, a);
+    const dim3 gi((a.n_items + per - 1) / per), gc((a.n_split + per - 1) / per);
+    if (a.pos) {  // a field's rows: the same walk and combine, the output row from the map
+        if (a.n_items > 0) agg_full_kernel<OP, T, VEC, G, true><<<gi, kBlock, 0, st>>>(X, out, a);
+        if (a.n_split > 0) agg_full_combine_kernel<OP, T, VEC, G, true><<<gc, kBlock, 0, st>>>(X, out, a);
+        return;
+    }
+    if (a.n_items > 0) agg_full_kernel<OP, T, VEC, G, false><<<gi, kBlock, 0, st>>>(X, out, a);
+    if (a.n_split > 0) agg_full_combine_kernel<OP, T, VEC, G, false><<<gc, kBlock, 0, st>>>(X, out, a);
 }
 
 template <int OP, typename T>
@@ -179,7 +188,8 @@ int64_t agg_full_ws_need(const FullPlan& p, int64_t F, int64_t row0, int64_t n_r
 
 void agg_full_launch(const FullPlan& p, const gs_full_plan_dev& d, gs_agg op, gs_dtype dt, const void* X, int64_t ldx,
                      int64_t F, const int64_t* row_ptr, const int32_t* col, int64_t row0, int64_t n_rows, void* out,
-                     int64_t ldo, void* ws, int64_t ws_bytes, hipStream_t st) {
+                     int64_t ldo, void* ws, int64_t ws_bytes, hipStream_t st, const FieldLayer* fl) {
+    GS_REQUIRE(!fl || (row0 == 0 && n_rows == p.n), GS_EINVAL, "a field covers the whole plan");
     GS_REQUIRE(op == GS_AGG_MEAN || op == GS_AGG_MAX, GS_EINVAL, "agg_func must be MEAN or MAX");
     GS_REQUIRE(dt == GS_F32 || dt == GS_BF16, GS_EINVAL, "dtype must be f32 or bf16");
     const int64_t need = agg_full_ws_need(p, F, row0, n_rows);
@@ -190,7 +200,7 @@ void agg_full_launch(const FullPlan& p, const gs_full_plan_dev& d, gs_agg op, gs
     if (op == GS_AGG_MAX && full_plan_empty_in(p, row0, n_rows) > 0)
         fail(GS_EEMPTY, "gs_agg_full: MAX aggregation over an empty neighbourhood (reference: models.py:321-325)");
     FullArgs a;
-    a.n_split = static_cast<int>(p.split_ptr[row0 + n_rows] - p.split_ptr[row0]);
+    a.n_split = fl ? static_cast<int>(fl->n_split) : static_cast<int>(p.split_ptr[row0 + n_rows] - p.split_ptr[row0]);
     GS_REQUIRE(need == 0 || (ws && ws_bytes >= need), GS_EINVAL, "workspace smaller than gs_agg_full_ws_bytes");
     GS_REQUIRE(a.n_split == 0 || d.split_rows, GS_EINVAL, "NULL split_rows");
     const int V = dt == GS_F32 ? 4 : 8;
@@ -212,6 +222,13 @@ void agg_full_launch(const FullPlan& p, const gs_full_plan_dev& d, gs_agg op, gs
     a.n_items = static_cast<int>(p.item_ptr[row0 + n_rows] - p.item_ptr[row0]);
     a.row0 = static_cast<int>(row0);
     a.gcn = p.gcn;
+    a.pos = nullptr;
+    if (fl) {
+        a.items = fl->items;
+        a.n_items = static_cast<int>(fl->n_items);
+        a.split_rows = fl->split;
+        a.pos = fl->pos;
+    }
     if (op == GS_AGG_MEAN) {
         if (dt == GS_F32) launch_full_t<GS_AGG_MEAN, float>(vec, static_cast<const float*>(X), static_cast<float*>(out), a, st);
         else launch_full_t<GS_AGG_MEAN, bf16_t>(vec, static_cast<const bf16_t*>(X), static_cast<bf16_t*>(out), a, st);

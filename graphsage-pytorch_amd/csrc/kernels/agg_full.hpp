@@ -2,6 +2,7 @@
 // Internal launcher of the full-neighbourhood aggregate (agg_full.hip), shared
 // with the layer-wise driver (infer_full.hip).  Throws gs::Error.
 #include "../host/full_plan.hpp"
+#include "full_field.hpp"
 #include "kcommon.hpp"
 
 namespace gs {
@@ -40,6 +41,7 @@ struct FullArgs {
     const int* split_rows;  // the window's first split row
     const int* cnt;
     const uint8_t* self_loop;
+    const int* pos;         // MAP kernels: the output row of a node (a field's pos_l); NULL otherwise
     float* part;
     int64_t slot0;          // slot_ptr[row0]: the window's partials start at part[0]
     int64_t seg_len;        // clamped to 2^31 - 1
@@ -52,17 +54,22 @@ int64_t agg_full_ws_need(const FullPlan& p, int64_t F, int64_t row0, int64_t n_r
 // gs_agg_full (its argument checks included; every check before the first launch).
 void agg_full_launch(const FullPlan& p, const gs_full_plan_dev& d, gs_agg op, gs_dtype dt, const void* X, int64_t ldx,
                      int64_t F, const int64_t* row_ptr, const int32_t* col, int64_t row0, int64_t n_rows, void* out,
-                     int64_t ldo, void* ws, int64_t ws_bytes, hipStream_t st);
+                     int64_t ldo, void* ws, int64_t ws_bytes, hipStream_t st, const FieldLayer* fl = nullptr);
+// `fl` (both forward launchers, row0 = 0 and n_rows = n): the field's items and split rows of R_l instead of
+// the plan's, row v written to row fl->pos[v] of a compact out (and argmax).
 // gs_agg_full_argmax / gs_agg_full_bwd (agg_full_bwd.hip; every check before the first launch)
 int64_t agg_full_argmax_ws_need(const FullPlan& p, int64_t F, int64_t row0, int64_t n_rows);
 void agg_full_argmax_launch(const FullPlan& p, const gs_full_plan_dev& d, gs_dtype dt, const void* X, int64_t ldx,
                             int64_t F, const int64_t* row_ptr, const int32_t* col, int64_t row0, int64_t n_rows,
                             void* out, int64_t ldo, int32_t* argmax, int64_t lda, void* ws, int64_t ws_bytes,
-                            hipStream_t st);
+                            hipStream_t st, const FieldLayer* fl = nullptr);
 int64_t agg_full_bwd_ws_need(const FullPlan& tp, int64_t F);
 void agg_full_bwd_launch(const FullPlan& tp, const gs_full_plan_dev& td, gs_agg op, int64_t F,
                          const int64_t* t_row_ptr, const int32_t* t_col, const float* dA, const float* dSelf,
                          int64_t ldd, const int32_t* argmax, int64_t lda, const float* Hprev, float* dH, int64_t ldh,
-                         void* ws, int64_t ws_bytes, hipStream_t st);
+                         void* ws, int64_t ws_bytes, hipStream_t st, const FieldLayer* fl = nullptr, int64_t ldo = 0);
+// `fl` (the backward): the transposed items and split rows of R_{l-1}; destinations v outside R_l are skipped,
+// dA / dSelf / argmax are compact in R_l order, Hprev is the N-row table (row stride ldh) and dH is compact in
+// R_{l-1} order with row stride ldo.
 
 }  // namespace gs

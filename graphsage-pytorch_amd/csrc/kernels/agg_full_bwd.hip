@@ -18,6 +18,13 @@
 // epilogue that adds the self-row gradient dSelf[u] and zeroes the row where
 // Hprev[u] <= 0 (the relu of the layer below), so dH_{l-1} leaves finished.
 // No atomics: a pure function of the inputs and seg_len.
+//
+// MAP (a template parameter, as in agg_full.hip): layer l of a receptive
+// field.  The forward writes row pos_l[v] of compact outputs; the backward
+// runs over the transposed items of R_{l-1}, masks a destination v outside
+// R_l like a slot past the segment, reads dA and argmax at row pos_l[v] (the
+// divisor cnt[v] and the compared ids stay global), adds dSelf[pos_l[u]]
+// only where u is in R_l, and writes row pos_{l-1}[u] of a compact dH.
 #include "agg_dev.hpp"
 #include "agg_full.hpp"
 
@@ -83,7 +90,7 @@ struct ArgmaxOut {
 };
 
 // gcn's missing self row (last, as the unsplit forward adds it) and the output rows.
-template <int VEC>
+template <int VEC, bool MAP>
 __device__ __forceinline__ void argmax_finish(const float* __restrict__ X, float* __restrict__ out, const FullArgs& a,
                                               const ArgmaxOut& o, int node, int f0, float (&acc)[VEC], int (&arg)[VEC]) {
     if (a.gcn && !a.self_loop[node]) {
@@ -96,11 +103,12 @@ __device__ __forceinline__ void argmax_finish(const float* __restrict__ X, float
             arg[v] = take ? node : arg[v];
         }
     }
-    RowIO<float, VEC>::store(out + static_cast<int64_t>(node - a.row0) * a.ldo + f0, acc);
-    put_ids<VEC>(o.am + static_cast<int64_t>(node - a.row0) * o.lda + f0, arg);
+    const int64_t orow = MAP ? a.pos[node] : node - a.row0;
+    RowIO<float, VEC>::store(out + orow * a.ldo + f0, acc);
+    put_ids<VEC>(o.am + orow * o.lda + f0, arg);
 }
 
-template <int VEC, int G>
+template <int VEC, int G, bool MAP>
 __global__ __launch_bounds__(kBlock) void agg_full_argmax_kernel(const float* __restrict__ X, float* __restrict__ out,
                                                                  FullArgs a, ArgmaxOut o) {
     constexpr int NR = kRows / 2;  // an id beside every accumulator: half the rows in flight
@@ -162,11 +170,11 @@ __global__ __launch_bounds__(kBlock) void agg_full_argmax_kernel(const float* __
             put_ids<VEC>(o.part_ids + po, arg);
             continue;
         }
-        argmax_finish<VEC>(X, out, a, o, node, f0, acc, arg);
+        argmax_finish<VEC, MAP>(X, out, a, o, node, f0, acc, arg);
     }
 }
 
-template <int VEC, int G>
+template <int VEC, int G, bool MAP>
 __global__ __launch_bounds__(kBlock) void agg_full_argmax_combine_kernel(const float* __restrict__ X,
                                                                          float* __restrict__ out, FullArgs a,
                                                                          ArgmaxOut o) {
@@ -201,17 +209,21 @@ __global__ __launch_bounds__(kBlock) void agg_full_argmax_combine_kernel(const f
                 arg[v] = take ? id[v] : arg[v];
             }
         }
-        argmax_finish<VEC>(X, out, a, o, node, f0, acc, arg);
+        argmax_finish<VEC, MAP>(X, out, a, o, node, f0, acc, arg);
     }
 }
 
 template <int VEC, int G>
 void launch_argmax(const float* X, float* out, const FullArgs& a, const ArgmaxOut& o, hipStream_t st) {
     constexpr int per = kBlock / G;
-    if (a.n_items > 0)
-        agg_full_argmax_kernel<VEC, G><<<dim3((a.n_items + per - 1) / per), kBlock, 0, st>>>(X, out, a, o);
-    if (a.n_split > 0)
-        agg_full_argmax_combine_kernel<VEC, G><<<dim3((a.n_split + per - 1) / per), kBlock, 0, st>>>(X, out, a, o);
+    const dim3 gi((a.n_items + per - 1) / per), gc((a.n_split + per - 1) / per);
+    if (a.pos) {  // a field's rows
+        if (a.n_items > 0) agg_full_argmax_kernel<VEC, G, true><<<gi, kBlock, 0, st>>>(X, out, a, o);
+        if (a.n_split > 0) agg_full_argmax_combine_kernel<VEC, G, true><<<gc, kBlock, 0, st>>>(X, out, a, o);
+        return;
+    }
+    if (a.n_items > 0) agg_full_argmax_kernel<VEC, G, false><<<gi, kBlock, 0, st>>>(X, out, a, o);
+    if (a.n_split > 0) agg_full_argmax_combine_kernel<VEC, G, false><<<gc, kBlock, 0, st>>>(X, out, a, o);
 }
 
 // ------------------------------------------------------------------ backward
@@ -230,17 +242,21 @@ struct BwdArgs {
     const float* Hprev;      // may be NULL
     float* dH;
     int64_t ldh;
+    const int* pos;          // MAP: a destination's row of dA / dSelf / am (a field's pos_l), -1: not in R_l
+    const int* opos;         // MAP: a source row's row of dH (pos_{l-1})
+    int64_t ldo;             // MAP: dH's row stride (Hprev keeps ldh)
     float* part;
     int64_t seg_len;         // clamped to 2^31 - 1
     int F, n_items, n_split;
 };
 
-// dH[u] = (acc + dSelf[u]) zeroed where Hprev[u] <= 0.
-template <int VEC>
+// dH[u] = (acc + dSelf[u]) zeroed where Hprev[u] <= 0.  MAP: dSelf only where u is in R_l, dH compact.
+template <int VEC, bool MAP>
 __device__ __forceinline__ void bwd_finish(const BwdArgs& a, int node, int f0, float (&acc)[VEC]) {
-    if (a.dSelf) {
+    const int64_t srow = MAP ? a.pos[node] : node;
+    if (a.dSelf && (!MAP || srow >= 0)) {
         float s[VEC];
-        RowIO<float, VEC>::load(a.dSelf + static_cast<int64_t>(node) * a.ldd + f0, s);
+        RowIO<float, VEC>::load(a.dSelf + srow * a.ldd + f0, s);
 #pragma unroll
         for (int v = 0; v < VEC; ++v) acc[v] += s[v];
     }
@@ -250,10 +266,11 @@ __device__ __forceinline__ void bwd_finish(const BwdArgs& a, int node, int f0, f
 #pragma unroll
         for (int v = 0; v < VEC; ++v) acc[v] = h[v] <= 0.f ? 0.f : acc[v];
     }
-    RowIO<float, VEC>::store(a.dH + static_cast<int64_t>(node) * a.ldh + f0, acc);
+    if (MAP) RowIO<float, VEC>::store(a.dH + static_cast<int64_t>(a.opos[node]) * a.ldo + f0, acc);
+    else RowIO<float, VEC>::store(a.dH + static_cast<int64_t>(node) * a.ldh + f0, acc);
 }
 
-template <int OP, int VEC, int G>
+template <int OP, int VEC, int G, bool MAP>
 __global__ __launch_bounds__(kBlock) void agg_full_bwd_kernel(BwdArgs a) {
     constexpr int NR = OP == GS_AGG_MAX ? kRows / 2 : kRows;  // MAX loads an id row beside every gradient row
     const int gl = threadIdx.x % G;
@@ -285,6 +302,7 @@ __global__ __launch_bounds__(kBlock) void agg_full_bwd_kernel(BwdArgs a) {
             // MAX routes a destination's gradient once, however often its row names this source (the
             // transposed row is ascending: repeats are neighbours, across a segment boundary too)
             else if (e > rb && a.col[e - 1] == nb) my = -1;
+            if (MAP && my >= 0) my = a.pos[nb];  // the destination's compact row; -1: outside R_l, skipped
             for (int j = 0; j < m; j += NR) {
                 int rows[NR];
                 float c[NR];
@@ -296,7 +314,7 @@ __global__ __launch_bounds__(kBlock) void agg_full_bwd_kernel(BwdArgs a) {
                     if constexpr (OP == GS_AGG_MEAN) c[u] = __shfl(cf, src, G);
                     ok[u] = (j + u < m) && rows[u] >= 0;
                 }
-                const int fallback = rows[0] >= 0 ? rows[0] : node;
+                const int fallback = rows[0] >= 0 ? rows[0] : (MAP ? 0 : node);  // R_l is never empty
                 float x[NR][VEC];
                 int id[OP == GS_AGG_MAX ? NR : 1][VEC];
 #pragma unroll
@@ -321,12 +339,12 @@ __global__ __launch_bounds__(kBlock) void agg_full_bwd_kernel(BwdArgs a) {
             part_store<VEC>(a.part + (a.slot_ptr[node] + seg) * F + f0, acc);
             continue;
         }
-        bwd_finish<VEC>(a, node, f0, acc);
+        bwd_finish<VEC, MAP>(a, node, f0, acc);
     }
 }
 
 // One lane group per split source row: its partial sums in segment order, four loads in flight.
-template <int VEC, int G>
+template <int VEC, int G, bool MAP>
 __global__ __launch_bounds__(kBlock) void agg_full_bwd_combine_kernel(BwdArgs a) {
     constexpr int NP = 4;
     const int gl = threadIdx.x % G;
@@ -356,16 +374,21 @@ __global__ __launch_bounds__(kBlock) void agg_full_bwd_combine_kernel(BwdArgs a)
                 for (int v = 0; v < VEC; ++v) acc[v] += ok ? x[u][v] : 0.f;
             }
         }
-        bwd_finish<VEC>(a, node, f0, acc);
+        bwd_finish<VEC, MAP>(a, node, f0, acc);
     }
 }
 
 template <int OP, int VEC, int G>
 void launch_bwd(const BwdArgs& a, hipStream_t st) {
     constexpr int per = kBlock / G;
-    if (a.n_items > 0) agg_full_bwd_kernel<OP, VEC, G><<<dim3((a.n_items + per - 1) / per), kBlock, 0, st>>>(a);
-    if (a.n_split > 0)
-        agg_full_bwd_combine_kernel<VEC, G><<<dim3((a.n_split + per - 1) / per), kBlock, 0, st>>>(a);
+    const dim3 gi((a.n_items + per - 1) / per), gc((a.n_split + per - 1) / per);
+    if (a.pos) {  // a field's rows
+        if (a.n_items > 0) agg_full_bwd_kernel<OP, VEC, G, true><<<gi, kBlock, 0, st>>>(a);
+        if (a.n_split > 0) agg_full_bwd_combine_kernel<VEC, G, true><<<gc, kBlock, 0, st>>>(a);
+        return;
+    }
+    if (a.n_items > 0) agg_full_bwd_kernel<OP, VEC, G, false><<<gi, kBlock, 0, st>>>(a);
+    if (a.n_split > 0) agg_full_bwd_combine_kernel<VEC, G, false><<<gc, kBlock, 0, st>>>(a);
 }
 
 template <int OP>
@@ -386,7 +409,8 @@ int64_t agg_full_argmax_ws_need(const FullPlan& p, int64_t F, int64_t row0, int6
 void agg_full_argmax_launch(const FullPlan& p, const gs_full_plan_dev& d, gs_dtype dt, const void* X, int64_t ldx,
                             int64_t F, const int64_t* row_ptr, const int32_t* col, int64_t row0, int64_t n_rows,
                             void* out, int64_t ldo, int32_t* argmax, int64_t lda, void* ws, int64_t ws_bytes,
-                            hipStream_t st) {
+                            hipStream_t st, const FieldLayer* fl) {
+    GS_REQUIRE(!fl || (row0 == 0 && n_rows == p.n), GS_EINVAL, "a field covers the whole plan");
     GS_REQUIRE(dt == GS_F32, GS_EINVAL, "gs_agg_full_argmax: fp32 rows only (a bf16 table's aggregate has no backward)");
     GS_REQUIRE(!p.transposed, GS_EINVAL, "gs_agg_full_argmax: a forward plan expected");
     const int64_t need = agg_full_argmax_ws_need(p, F, row0, n_rows);
@@ -397,7 +421,7 @@ void agg_full_argmax_launch(const FullPlan& p, const gs_full_plan_dev& d, gs_dty
     if (full_plan_empty_in(p, row0, n_rows) > 0)
         fail(GS_EEMPTY, "gs_agg_full_argmax: MAX aggregation over an empty neighbourhood (reference: models.py:321-325)");
     FullArgs a;
-    a.n_split = static_cast<int>(p.split_ptr[row0 + n_rows] - p.split_ptr[row0]);
+    a.n_split = fl ? static_cast<int>(fl->n_split) : static_cast<int>(p.split_ptr[row0 + n_rows] - p.split_ptr[row0]);
     GS_REQUIRE(need == 0 || (ws && ws_bytes >= need), GS_EINVAL,
                "workspace smaller than gs_agg_full_argmax_ws_bytes");
     GS_REQUIRE(a.n_split == 0 || d.split_rows, GS_EINVAL, "NULL split_rows");
@@ -419,6 +443,13 @@ void agg_full_argmax_launch(const FullPlan& p, const gs_full_plan_dev& d, gs_dty
     a.n_items = static_cast<int>(p.item_ptr[row0 + n_rows] - p.item_ptr[row0]);
     a.row0 = static_cast<int>(row0);
     a.gcn = p.gcn;
+    a.pos = nullptr;
+    if (fl) {
+        a.items = fl->items;
+        a.n_items = static_cast<int>(fl->n_items);
+        a.split_rows = fl->split;
+        a.pos = fl->pos;
+    }
     ArgmaxOut o;
     o.am = argmax;
     o.lda = lda;
@@ -445,9 +476,10 @@ int64_t agg_full_bwd_ws_need(const FullPlan& tp, int64_t F) {
 void agg_full_bwd_launch(const FullPlan& tp, const gs_full_plan_dev& td, gs_agg op, int64_t F,
                          const int64_t* t_row_ptr, const int32_t* t_col, const float* dA, const float* dSelf,
                          int64_t ldd, const int32_t* argmax, int64_t lda, const float* Hprev, float* dH, int64_t ldh,
-                         void* ws, int64_t ws_bytes, hipStream_t st) {
+                         void* ws, int64_t ws_bytes, hipStream_t st, const FieldLayer* fl, int64_t ldo) {
     GS_REQUIRE(op == GS_AGG_MEAN || op == GS_AGG_MAX, GS_EINVAL, "agg_func must be MEAN or MAX");
     const int64_t need = agg_full_bwd_ws_need(tp, F);
+    GS_REQUIRE(!fl || ldo >= F, GS_EINVAL, "leading dimension smaller than F");
     GS_REQUIRE(ldd >= F && ldh >= F && (op != GS_AGG_MAX || lda >= F), GS_EINVAL, "leading dimension smaller than F");
     if (tp.n == 0) return;
     GS_REQUIRE(t_row_ptr && t_col && dA && dH && td.items && td.slot_ptr && td.count, GS_EINVAL, "NULL device pointer");
@@ -456,7 +488,7 @@ void agg_full_bwd_launch(const FullPlan& tp, const gs_full_plan_dev& td, gs_agg 
     BwdArgs a;
     a.n_split = static_cast<int>(tp.split_rows.size());
     GS_REQUIRE(a.n_split == 0 || td.split_rows, GS_EINVAL, "NULL split_rows");
-    const bool vec = F % 4 == 0 && ldd % 4 == 0 && ldh % 4 == 0 && aligned16(dA) && aligned16(dH) &&
+    const bool vec = F % 4 == 0 && ldd % 4 == 0 && ldh % 4 == 0 && (!fl || ldo % 4 == 0) && aligned16(dA) && aligned16(dH) &&
                      (!dSelf || aligned16(dSelf)) && (!Hprev || aligned16(Hprev)) &&
                      (op != GS_AGG_MAX || (lda % 4 == 0 && aligned16(argmax))) && (need == 0 || aligned16(ws));
     a.row_ptr = t_row_ptr;
@@ -477,6 +509,17 @@ void agg_full_bwd_launch(const FullPlan& tp, const gs_full_plan_dev& td, gs_agg 
     a.seg_len = std::min<int64_t>(tp.seg_len, (int64_t(1) << 31) - 1);
     a.F = static_cast<int>(F);
     a.n_items = static_cast<int>(tp.items.size() / 2);
+    a.pos = a.opos = nullptr;
+    a.ldo = ldh;
+    if (fl) {
+        a.items = fl->t_items;
+        a.n_items = static_cast<int>(fl->n_t_items);
+        a.split_rows = fl->t_split;
+        a.n_split = static_cast<int>(fl->n_t_split);
+        a.pos = fl->pos;
+        a.opos = fl->pos_prev;
+        a.ldo = ldo;
+    }
     if (op == GS_AGG_MEAN) launch_bwd_t<GS_AGG_MEAN>(vec, a, st);
     else launch_bwd_t<GS_AGG_MAX>(vec, a, st);
     check_launch("gs_agg_full_bwd");
@@ -524,6 +567,39 @@ int gs_agg_full_bwd(const gs_full_plan* tplan, const gs_full_plan_dev* tdev, gs_
     GS_REQUIRE(tplan && tdev, GS_EINVAL, "NULL plan");
     gs::agg_full_bwd_launch(*reinterpret_cast<const gs::FullPlan*>(tplan), *tdev, op, F, t_row_ptr, t_col, dA, dSelf,
                             ldd, argmax, lda, Hprev, dH, ldh, ws, ws_bytes, gs::as_stream(stream));
+    GS_API_END
+}
+
+int gs_agg_full_field(const gs_full_plan* plan, const gs_full_plan_dev* dev, const gs_full_plan* tplan,
+                      const gs_full_field* f, int32_t layer, gs_agg op, gs_dtype dt, const void* X, int64_t ldx,
+                      int64_t F, const int64_t* row_ptr, const int32_t* col, void* out, int64_t ldo, int32_t* argmax,
+                      int64_t lda, void* ws, int64_t ws_bytes, void* stream) {
+    GS_API_BEGIN
+    GS_REQUIRE(plan && dev && tplan && f, GS_EINVAL, "NULL argument");
+    const gs::FullPlan& p = *reinterpret_cast<const gs::FullPlan*>(plan);
+    const gs::FieldLayer fl = gs::field_layer(p, *reinterpret_cast<const gs::FullPlan*>(tplan), *f, layer);
+    if (argmax) {
+        GS_REQUIRE(op == GS_AGG_MAX, GS_EINVAL, "argmax is recorded for MAX only");
+        gs::agg_full_argmax_launch(p, *dev, dt, X, ldx, F, row_ptr, col, 0, p.n, out, ldo, argmax, lda, ws, ws_bytes,
+                                   gs::as_stream(stream), &fl);
+    } else {
+        gs::agg_full_launch(p, *dev, op, dt, X, ldx, F, row_ptr, col, 0, p.n, out, ldo, ws, ws_bytes,
+                            gs::as_stream(stream), &fl);
+    }
+    GS_API_END
+}
+
+int gs_agg_full_bwd_field(const gs_full_plan* plan, const gs_full_plan* tplan, const gs_full_plan_dev* tdev,
+                          const gs_full_field* f, int32_t layer, gs_agg op, int64_t F, const int64_t* t_row_ptr,
+                          const int32_t* t_col, const float* dA, const float* dSelf, int64_t ldd,
+                          const int32_t* argmax, int64_t lda, const float* Hprev, int64_t ldh, float* dH, int64_t ldo,
+                          void* ws, int64_t ws_bytes, void* stream) {
+    GS_API_BEGIN
+    GS_REQUIRE(plan && tplan && tdev && f, GS_EINVAL, "NULL argument");
+    const gs::FullPlan& tp = *reinterpret_cast<const gs::FullPlan*>(tplan);
+    const gs::FieldLayer fl = gs::field_layer(*reinterpret_cast<const gs::FullPlan*>(plan), tp, *f, layer);
+    gs::agg_full_bwd_launch(tp, *tdev, op, F, t_row_ptr, t_col, dA, dSelf, ldd, argmax, lda, Hprev, dH,
+                            Hprev ? ldh : std::max(ldh, F), ws, ws_bytes, gs::as_stream(stream), &fl, ldo);
     GS_API_END
 }
 

@@ -184,9 +184,130 @@ void train_full_run(const FullPlan& p, const gs_full_plan_dev& d, const FullPlan
     }
 }
 
+namespace {
+
+// D[map[nodes[i]]] = E[i]: the loss head's rows into the compact dH_L (map: the field's pos_L).
+__global__ __launch_bounds__(256) void rows_by_map_kernel(float* __restrict__ D, const float* __restrict__ E,
+                                                          const int* __restrict__ nodes, const int* __restrict__ map,
+                                                          int64_t B, int q) {
+    const int64_t t = blockIdx.x * int64_t(256) + threadIdx.x;
+    if (t >= B * q) return;
+    const int64_t i = t / q;
+    const int c = static_cast<int>(t % q);
+    const int r = map[nodes[i]];
+    if (r < 0) return;  // not a root of this field: refused on the host before any launch
+    reinterpret_cast<float4*>(D)[static_cast<int64_t>(r) * q + c] = reinterpret_cast<const float4*>(E)[t];
+}
+
+}  // namespace
+
+// train_full_run restricted to the receptive field of `nodes` (full_field.hip).  The H_l tables stay N-row and
+// indexed by global id, so col and the gather loop are unchanged: layer l scatters its n_l output rows into H_l
+// and reads H_{l-1} on R_{l-1}, which layer l - 1 wrote.  A_l, argmax_l, dSelf and dA are compact in R_l order, and
+// so is dH_l (unlike H_l: the GEMMs read dZ_l as n_l consecutive rows, the workspace has no spare [n_l, H]
+// buffer to gather them into when L == 1, and the backward aggregate can write row pos_{l-1}[u] as cheaply as
+// row u).  The forward GEMM's compact output waits in dH's first buffer, which is free until the head.  No
+// launch here works on N x width: no memset of dH_L (the head's rows are R_L, each written in full), and the
+// restricted backward writes every row of R_{l-1}.
+void train_full_field_run(const FullPlan& p, const gs_full_plan_dev& d, const FullPlan& tp, const gs_full_plan_dev& td,
+                          const gs_train_full_config& c, const gs_full_field& f, const int32_t* nodes, int64_t B,
+                          int reuse_agg1, int stages, float* loss, void* ws, int64_t ws_bytes, hipStream_t st) {
+    const TrainLayout lo = layout_of(p, tp, c);
+    const int64_t H = c.hidden, L = c.n_layers, C = c.n_classes, m = p.gcn ? 1 : 2;
+    GS_REQUIRE(c.X && c.row_ptr && c.col && c.t_row_ptr && c.t_col && c.labels && c.params && c.grads && loss,
+               GS_EINVAL, "NULL pointer");
+    GS_REQUIRE(nodes && B >= 1 && B <= c.max_nodes, GS_EINVAL, "nodes: 1 to max_nodes ids");
+    GS_REQUIRE(stages >= 1 && stages <= GS_TF_ALL, GS_EINVAL, "bad stages");
+    GS_REQUIRE(ws && ws_bytes >= lo.total && (reinterpret_cast<uintptr_t>(ws) & (kAlign - 1)) == 0, GS_EINVAL,
+               "workspace smaller than gs_train_full_ws_bytes or not 256-byte aligned");
+    GS_REQUIRE(aligned16(c.params) && aligned16(c.grads), GS_EINVAL, "params / grads must be 16-byte aligned");
+    GS_REQUIRE(f.n_layers == L, GS_EINVAL, "the field was built for another number of layers");
+    if (!p.empty_rows.empty())
+        fail(GS_EEMPTY, "gs_train_full: a node's effective neighbourhood is empty (reference: models.py:313, :321-325)");
+    FieldLayer fl[GS_MAX_HOPS + 1];
+    for (int l = 1; l <= L; ++l) fl[l] = field_layer(p, tp, f, l);
+    GS_REQUIRE(fl[L].n == B, GS_EINVAL, "the field was built for another set of nodes");
+    char* base = static_cast<char*>(ws);
+    const gs_agg op = static_cast<gs_agg>(c.agg);
+    auto fptr = [&](int64_t o) { return reinterpret_cast<float*>(base + o); };
+    int64_t woff[GS_MAX_HOPS + 1];
+    woff[0] = 0;
+    for (int l = 1; l <= L; ++l) woff[l] = woff[l - 1] + H * m * in_width(c, l);
+    const int64_t wc_off = woff[L], bc_off = wc_off + C * H;
+    const int q = static_cast<int>(H / 4);
+
+    if (stages & GS_TF_FORWARD) {
+        if (lo.w1lp >= 0) ok(gs_cast_f32_bf16(c.params, base + lo.w1lp, H * m * c.feat_dim, st));
+        float* tmp = fptr(lo.dh[0]);  // the GEMM's compact output rows, scattered into H_l
+        for (int l = 1; l <= L; ++l) {
+            const gs_dtype dt = l == 1 ? static_cast<gs_dtype>(c.feat_dtype) : GS_F32;
+            const char* in = l == 1 ? static_cast<const char*>(c.X) : base + lo.h[l - 2];
+            const int64_t ldin = l == 1 ? c.feat_ld : H, fin = in_width(c, l), nl = fl[l].n;
+            if (lo.am[l - 1] >= 0)
+                agg_full_argmax_launch(p, d, dt, in, ldin, fin, c.row_ptr, c.col, 0, p.n, base + lo.a[l - 1], fin,
+                                       reinterpret_cast<int32_t*>(base + lo.am[l - 1]), fin, base + lo.part,
+                                       lo.part_bytes, st, &fl[l]);
+            else if (l > 1 || !reuse_agg1)
+                agg_full_launch(p, d, op, dt, in, ldin, fin, c.row_ptr, c.col, 0, p.n, base + lo.a[l - 1], fin,
+                                base + lo.part, lo.part_bytes, st, &fl[l]);
+            const void* W = (l == 1 && lo.w1lp >= 0) ? static_cast<const void*>(base + lo.w1lp)
+                                                     : static_cast<const void*>(c.params + woff[l - 1]);
+            linear_fwd_launch(dt, nl, fin, H, p.gcn ? nullptr : in, ldin, fl[l].rows, base + lo.a[l - 1], fin, W, tmp,
+                              H, 1, st);
+            rows_by_id_kernel<true><<<dim3(static_cast<unsigned>((nl * q + 255) / 256)), 256, 0, st>>>(
+                fptr(lo.h[l - 1]), tmp, fl[l].rows, nl, q);
+            check_launch("gs_train_full_field(scatter H)");
+        }
+    }
+    float* dh_top = fptr(lo.dh[(L - 1) % 2]);
+    if (stages & GS_TF_HEAD) {
+        const unsigned grid = static_cast<unsigned>((B * q + 255) / 256);
+        rows_by_id_kernel<false><<<dim3(grid), 256, 0, st>>>(fptr(lo.h[L - 1]), fptr(lo.e), nodes, B, q);
+        check_launch("gs_train_full_field(gather)");
+        ok(gs_cls_nll_fwd_bwd(B, H, C, fptr(lo.e), c.params + wc_off, c.params + bc_off, c.labels, nodes, 1, loss,
+                              fptr(lo.de), c.grads + wc_off, c.grads + bc_off, fptr(lo.cls), st));
+        // dZ_L, compact: R_L is `nodes`, so every one of its n_L rows is written
+        rows_by_map_kernel<<<dim3(grid), 256, 0, st>>>(dh_top, fptr(lo.de), nodes, fl[L].pos, B, q);
+        check_launch("gs_train_full_field(scatter dE)");
+    }
+    if (stages & GS_TF_BACKWARD) {
+        for (int l = static_cast<int>(L); l >= 1; --l) {
+            const gs_dtype dt = l == 1 ? static_cast<gs_dtype>(c.feat_dtype) : GS_F32;
+            const char* in = l == 1 ? static_cast<const char*>(c.X) : base + lo.h[l - 2];
+            const int64_t ldin = l == 1 ? c.feat_ld : H, fin = in_width(c, l), nl = fl[l].n;
+            const float* dz = fptr(lo.dh[(l - 1) % 2]);  // dH_l on R_l, already masked by relu'(H_l)
+            float* dW = c.grads + woff[l - 1];
+            const int S = linear_dw_slabs(dt, nl, fin, H, p.gcn ? nullptr : in, ldin, fl[l].rows, base + lo.a[l - 1],
+                                          fin, dz, nullptr, H, 0, dW, base + lo.slab, lo.slab_bytes, st, -1,
+                                          nl >= 512 ? kDw1Phases : 1);
+            if (S > 1) sum_slabs_launch(fptr(lo.slab), S, H * m * fin, dW, nullptr, st);
+            if (l == 1) break;  // the feature table has no gradient
+            float* dself = p.gcn ? nullptr : fptr(lo.dself);
+            ok(gs_sage_linear_bwd_input(nl, H, H, dz, nullptr, H, 0, c.params + woff[l - 1], dself, fptr(lo.da), H, st));
+            agg_full_bwd_launch(tp, td, op, H, c.t_row_ptr, c.t_col, fptr(lo.da), dself, H,
+                                lo.am[l - 1] >= 0 ? reinterpret_cast<const int32_t*>(base + lo.am[l - 1]) : nullptr, H,
+                                fptr(lo.h[l - 2]), fptr(lo.dh[(l - 2) % 2]), H, base + lo.part, lo.part_bytes, st,
+                                &fl[l], H);
+        }
+    }
+}
+
 }  // namespace gs
 
 extern "C" {
+
+int gs_train_full_field_forward_backward(const gs_full_plan* plan, const gs_full_plan_dev* dev,
+                                         const gs_full_plan* tplan, const gs_full_plan_dev* tdev,
+                                         const gs_train_full_config* cfg, const gs_full_field* f,
+                                         const int32_t* nodes, int64_t n_nodes, int32_t reuse_agg1, int32_t stages,
+                                         float* loss, void* ws, int64_t ws_bytes, void* stream) {
+    GS_API_BEGIN
+    GS_REQUIRE(plan && dev && tplan && tdev && cfg && f, GS_EINVAL, "NULL argument");
+    gs::train_full_field_run(*reinterpret_cast<const gs::FullPlan*>(plan), *dev,
+                             *reinterpret_cast<const gs::FullPlan*>(tplan), *tdev, *cfg, *f, nodes, n_nodes, reuse_agg1,
+                             stages, loss, ws, ws_bytes, gs::as_stream(stream));
+    GS_API_END
+}
 
 int64_t gs_train_full_ws_bytes(const gs_full_plan* plan, const gs_full_plan* tplan, const gs_train_full_config* cfg) {
     try {

@@ -190,7 +190,8 @@ class FullPlan:
             self._h = None
 
 
-def agg_full(agg_func, X, graph, out=None, *, gcn=False, seg_len=None, row0=0, n_rows=None, ws=None, argmax=None):
+def agg_full(agg_func, X, graph, out=None, *, gcn=False, seg_len=None, row0=0, n_rows=None, ws=None, argmax=None,
+             field=None, layer=None):
     """Full-neighbourhood mean/max of rows of X over the device CSR for the
     destination rows [row0, row0 + n_rows) (gs_agg_full): adj[v] without v, or
     with v exactly once under gcn; rows longer than `seg_len` entries are
@@ -202,10 +203,24 @@ def agg_full(agg_func, X, graph, out=None, *, gcn=False, seg_len=None, row0=0, n
     fp32 rows only; an int32 [n_rows, F] tensor): also filled with the id of
     each element's first maximal source in the kernel's visiting order (CSR
     row order, gcn's missing self row last), which agg_full_bwd routes the
-    gradient to; `out` is bitwise the same with and without it."""
+    gradient to; `out` is bitwise the same with and without it.
+    `field`, `layer` (a ReceptiveField of this plan, 1 <= layer <= its depth):
+    only the rows of R_layer, row v as row field.pos(layer)[v] of a compact
+    [n_layer, F] out (and argmax, which still holds global source ids); every
+    row is bitwise the unrestricted call's (gs_agg_full_field)."""
     _dev(X, out, ws, argmax)
     import ctypes
     plan = graph if isinstance(graph, FullPlan) else agg_full_plan(graph, gcn=gcn, seg_len=seg_len)
+    if field is not None:
+        if field.plan is not plan or not field.build_id:
+            raise ValueError("agg_full: the field was built for another plan (or not built)")
+        if layer is None or not 1 <= int(layer) <= field.n_layers:
+            raise ValueError("agg_full: layer must lie in 1 .. field.n_layers")
+        if row0 != 0 or n_rows is not None:
+            raise ValueError("agg_full: a field takes no row window")
+        n_rows = field.size(int(layer))
+    elif layer is not None:
+        raise ValueError("agg_full: layer goes with a field")
     if X.dtype not in _DT:
         raise TypeError("X must be float32 or bfloat16")
     if argmax is not None and (agg_op(agg_func) != _lib.GS_AGG_MAX or X.dtype != torch.float32):
@@ -217,7 +232,7 @@ def agg_full(agg_func, X, graph, out=None, *, gcn=False, seg_len=None, row0=0, n
     row0 = int(row0)
     F = X.shape[1]
     ws_fn = lib().gs_agg_full_ws_bytes if argmax is None else lib().gs_agg_full_argmax_ws_bytes
-    need = int(ws_fn(plan.handle, F, row0, n_rows))
+    need = int(ws_fn(plan.handle, F, row0, n_rows if field is None else plan.n_nodes))
     if need < 0:
         check(_lib.GS_EINVAL)
     if out is None:
@@ -231,6 +246,14 @@ def agg_full(agg_func, X, graph, out=None, *, gcn=False, seg_len=None, row0=0, n
         if argmax.dtype != torch.int32 or argmax.dim() != 2 or argmax.stride(1) != 1 or argmax.shape[0] < n_rows or \
                 argmax.shape[1] < F:
             raise ValueError("argmax must be int32 [n_rows, F]")
+    if field is not None:
+        check(lib().gs_agg_full_field(plan.handle, ctypes.byref(d), field.tplan.handle, field.ref, int(layer),
+                                      agg_op(agg_func), _DT[X.dtype], ptr(X), X.stride(0), F, ptr(rp), ptr(cl),
+                                      ptr(out), out.stride(0), ptr(argmax),
+                                      argmax.stride(0) if argmax is not None else 0, ptr(ws),
+                                      ws.numel() * ws.element_size(), _stream(X)))
+        return out
+    if argmax is not None:
         check(lib().gs_agg_full_argmax(plan.handle, ctypes.byref(d), _DT[X.dtype], ptr(X), X.stride(0), F, ptr(rp),
                                        ptr(cl), row0, n_rows, ptr(out), out.stride(0), ptr(argmax), argmax.stride(0),
                                        ptr(ws), ws.numel() * ws.element_size(), _stream(X)))
@@ -258,15 +281,30 @@ def agg_full_bwd_plan(graph, *, gcn=False, seg_len=None):
 
 
 def agg_full_bwd(agg_func, dA, graph, dH=None, *, gcn=False, seg_len=None, dSelf=None, argmax=None, Hprev=None,
-                 ws=None):
+                 ws=None, field=None, layer=None):
     """Backward of agg_full over all rows (gs_agg_full_bwd), fp32:
     dH[u] = sum over the destinations v that read u of dA[v] / count[v] (MEAN)
     or of dA[v] where argmax[v] == u (MAX; `argmax` from agg_full), plus
     dSelf[u], zeroed where Hprev[u] <= 0 (both optional).  `graph` is a
     CSRGraph (its transposed plan for (gcn, seg_len) is built once and kept)
-    or a FullPlan, forward or transposed.  No atomics: bitwise repeatable."""
+    or a FullPlan, forward or transposed.  No atomics: bitwise repeatable.
+    `field`, `layer` (a ReceptiveField over this transposed plan): the
+    backward of layer `layer` into the rows u of R_{layer-1} only
+    (gs_agg_full_bwd_field).  dA, dSelf and argmax are then compact in R_layer
+    order ([n_layer, F]; destinations outside R_layer are skipped, dSelf is
+    added only where u is in R_layer), Hprev stays the [n_nodes, F] table,
+    and dH is compact in R_{layer-1} order ([n_{layer-1}, F])."""
     _dev(dA, dH, dSelf, argmax, Hprev, ws)
     import ctypes
+    if field is not None:
+        tplan = field.tplan
+        if isinstance(graph, FullPlan) and graph is not tplan and graph is not field.plan:
+            raise ValueError("agg_full_bwd: the field was built for another plan")
+        if not field.build_id or layer is None or not 1 <= int(layer) <= field.n_layers:
+            raise ValueError("agg_full_bwd: a built field and a layer in 1 .. field.n_layers expected")
+        return _agg_full_bwd_field(agg_func, dA, field, int(layer), dH, dSelf, argmax, Hprev, ws)
+    if layer is not None:
+        raise ValueError("agg_full_bwd: layer goes with a field")
     if isinstance(graph, FullPlan):
         tplan = graph if graph.is_transposed else graph.transposed()
     else:
@@ -298,6 +336,239 @@ def agg_full_bwd(agg_func, dA, graph, dH=None, *, gcn=False, seg_len=None, dSelf
     check(lib().gs_agg_full_bwd(tplan.handle, ctypes.byref(d), op, F, ptr(rp), ptr(cl), ptr(dA), ptr(dSelf),
                                 dA.stride(0), ptr(argmax), argmax.stride(0) if argmax is not None else 0, ptr(Hprev),
                                 ptr(dH), dH.stride(0), ptr(ws), ws.numel() * ws.element_size(), _stream(dA)))
+    return dH
+
+
+# ------------------------------------------------- the receptive field of a batch
+class HostField:
+    """full_field_host's result: rows(l) (ascending int32 ids of R_l), pos(l)
+    (int32 [N]: id -> index in rows(l), -1 outside) and sizes (n_L .. n_0)."""
+
+    def __init__(self, rows, n):
+        import numpy as np
+        self._rows = rows
+        self._pos = []
+        for r in rows:
+            p = np.full(n, -1, np.int32)
+            p[r] = np.arange(len(r), dtype=np.int32)
+            self._pos.append(p)
+        self.n_layers = len(rows) - 1
+        self.sizes = tuple(len(rows[l]) for l in range(self.n_layers, -1, -1))
+
+    def rows(self, l):
+        return self._rows[l]
+
+    def pos(self, l):
+        return self._pos[l]
+
+
+def full_field_host(row_ptr, col, nodes, n_layers, gcn=False):
+    """The L-hop receptive field of `nodes` in plain numpy, the CPU reference
+    of full_field (as sampler.fast_sample is of the Philox sampler):
+        R_L = nodes,  R_{l-1} = R_l U N_eff(R_l)
+    with N_eff(v) the plan's effective neighbourhood: v's CSR row without v's
+    own id.  Under `gcn` the row itself joins its neighbourhood, which changes
+    nothing here: it is in R_l already."""
+    import numpy as np
+    row_ptr = np.asarray(row_ptr, np.int64)
+    col = np.asarray(col, np.int64)
+    n = len(row_ptr) - 1
+    nodes = np.asarray(nodes, np.int64).reshape(-1)
+    if nodes.size < 1 or nodes.min() < 0 or nodes.max() >= n:
+        raise IndexError("full_field_host: node id out of range")
+    if len(np.unique(nodes)) != nodes.size:
+        raise ValueError("full_field_host: duplicate ids in nodes")
+    L = int(n_layers)
+    member = np.zeros(n, bool)
+    member[nodes] = True
+    rows = [None] * (L + 1)
+    for l in range(L, -1, -1):
+        rows[l] = np.nonzero(member)[0].astype(np.int32)
+        if l == 0:
+            break
+        for v in rows[l]:
+            nb = col[row_ptr[v]:row_ptr[v + 1]]
+            member[nb[nb != v]] = True
+    return HostField(rows, n)
+
+
+_field_builds = 0
+
+
+class ReceptiveField:
+    """The receptive field of a mini-batch on the device (gs_full_field_*):
+    owns the buffer the build fills for one (forward plan, transposed plan,
+    n_layers).  build(nodes) finds the field of `nodes` -- every launch on the
+    current stream, one host synchronisation at the end for the counts -- and
+    may be called again for the next mini-batch: the maps are then reset by
+    walking the old rows.  rows(l) / pos(l): R_l ascending and its inverse
+    map; items(l) / split(l) / t_items(l) / t_split(l): the plans' work items
+    and split rows restricted to R_l (transposed: to R_{l-1}); sizes: (n_L,
+    .., n_0).  `build_id` changes with every build."""
+
+    def __init__(self, plan, tplan, n_layers, device):
+        import ctypes
+        if not isinstance(plan, FullPlan) or plan.is_transposed or not isinstance(tplan, FullPlan) or \
+                not tplan.is_transposed:
+            raise ValueError("ReceptiveField: a forward FullPlan and its transposed plan expected")
+        self.plan, self.tplan, self.n_layers, self.device = plan, tplan, int(n_layers), torch.device(device)
+        need = int(lib().gs_full_field_bytes(plan.handle, tplan.handle, self.n_layers))
+        if need < 0:
+            check(_lib.GS_EINVAL)
+        self._buf = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+        self._off = (-self._buf.data_ptr()) % 256
+        self._f = _lib.FullField(n_layers=self.n_layers, buf=self._buf.data_ptr() + self._off, buf_bytes=need)
+        self._built = False
+        self.build_id = 0
+        self.nodes = None
+        self.sizes = ()
+        self._ref = ctypes.byref(self._f)
+
+    def build(self, nodes):
+        """`nodes`: a device int32 vector of unique ids in [0, N) (checked by the caller)."""
+        import ctypes
+        global _field_builds
+        if self._buf is None:
+            raise RuntimeError("ReceptiveField: released")
+        _dev(nodes)
+        if nodes.dtype != torch.int32 or nodes.dim() != 1 or not nodes.is_contiguous() or nodes.numel() < 1:
+            raise TypeError("ReceptiveField: nodes must be a contiguous 1-D int32 device tensor")
+        d, rp, cl = self.plan.device(self.device)
+        td, _trp, _tcl = self.tplan.device(self.device)
+        st = _lib.stream_ptr(self.device)
+        check(lib().gs_full_field_build(self.plan.handle, ctypes.byref(d), self.tplan.handle, ctypes.byref(td),
+                                        ptr(rp), ptr(cl), ptr(nodes), nodes.numel(), int(self._built), self._ref, st))
+        self._built = True
+        check(lib().gs_full_field_counts(self.plan.handle, self.tplan.handle, self._ref, st))
+        _field_builds += 1
+        self.build_id = _field_builds
+        self.nodes, self._nodes_version = nodes, nodes._version
+        self.sizes = tuple(int(self._f.counts[l]) for l in range(self.n_layers, -1, -1))
+        return self
+
+    def size(self, l):
+        return int(self._f.counts[l])
+
+    def layer_counts(self, l):
+        """(items, split rows, transposed items, transposed split rows) of layer l."""
+        c0 = _lib.GS_FF_LAYER0 + 4 * (l - 1)
+        return tuple(int(self._f.counts[c0 + k]) for k in range(4))
+
+    def _view(self, which, level, count, width=1):
+        if not self.build_id:
+            raise RuntimeError("ReceptiveField: not built")
+        off = int(lib().gs_full_field_offset(self.plan.handle, self.tplan.handle, self.n_layers, which, level))
+        if off < 0:
+            raise ValueError("ReceptiveField: level outside the field")
+        raw = self._buf[self._off + off:self._off + off + 4 * count * width].view(torch.int32)
+        return raw.view(count, width) if width > 1 else raw
+
+    def rows(self, l):
+        return self._view(_lib.GS_FF_ROWS, l, self.size(l))
+
+    def pos(self, l):
+        return self._view(_lib.GS_FF_POS, l, self.plan.n_nodes)
+
+    def items(self, l):
+        return self._view(_lib.GS_FF_ITEMS, l, self.layer_counts(l)[0], 2)
+
+    def split(self, l):
+        return self._view(_lib.GS_FF_SPLIT, l, self.layer_counts(l)[1])
+
+    def t_items(self, l):
+        return self._view(_lib.GS_FF_T_ITEMS, l, self.layer_counts(l)[2], 2)
+
+    def t_split(self, l):
+        return self._view(_lib.GS_FF_T_SPLIT, l, self.layer_counts(l)[3])
+
+    def covers(self, nodes):
+        """True when `nodes` (a device int32 vector of unique ids) is the set this field was built for."""
+        if nodes is self.nodes and nodes._version == self._nodes_version:
+            return True
+        if nodes.numel() != self.size(self.n_layers):
+            return False
+        return bool(torch.equal(torch.sort(nodes).values, self.rows(self.n_layers)))
+
+    def release(self):
+        """Free the buffer (the maps go with it); the object cannot be built again."""
+        self._buf = None
+        self.build_id = 0
+        self.nodes = None
+
+    @property
+    def ref(self):
+        return self._ref
+
+
+def _field_nodes(nodes, n, device):
+    """`nodes` as a device int32 vector of unique ids in [0, n), checked before any launch."""
+    import numpy as np
+    if isinstance(nodes, torch.Tensor) and nodes.is_cuda:
+        if nodes.dtype != torch.int32 or nodes.dim() != 1 or not nodes.is_contiguous() or nodes.numel() < 1:
+            raise TypeError("full_field: nodes must be a contiguous 1-D int32 tensor")
+        if int(nodes.min()) < 0 or int(nodes.max()) >= n:
+            raise IndexError("full_field: node id out of range")
+        if int(torch.unique(nodes).numel()) != nodes.numel():
+            raise ValueError("full_field: duplicate ids in nodes")
+        return nodes
+    a = np.asarray(nodes.cpu() if isinstance(nodes, torch.Tensor) else nodes)
+    if a.ndim != 1 or a.size < 1 or a.dtype.kind not in "iu":
+        raise TypeError("full_field: nodes must be a 1-D array of integer ids")
+    if a.min() < 0 or a.max() >= n:
+        raise IndexError("full_field: node id out of range")
+    if len(np.unique(a)) != a.size:
+        raise ValueError("full_field: duplicate ids in nodes")
+    return torch.from_numpy(a.astype(np.int32)).to(device)
+
+
+def full_field(plan, tplan, nodes, n_layers, device=None, out=None):
+    """The receptive field of `nodes` over `n_layers` layers, found on the
+    device (gs_full_field_build): a ReceptiveField that owns its buffers.
+    `nodes`: unique ids, a device int32 vector or a host array (then `device`
+    says where to build; default cuda).  `out`: a ReceptiveField of the same
+    plans and depth to rebuild in place.  full_field_host is the CPU mirror."""
+    if device is None:
+        device = nodes.device if isinstance(nodes, torch.Tensor) and nodes.is_cuda else torch.device("cuda")
+    nodes = _field_nodes(nodes, plan.n_nodes, device)
+    if out is None:
+        out = ReceptiveField(plan, tplan, n_layers, device)
+    elif out.plan is not plan or out.tplan is not tplan or out.n_layers != int(n_layers):
+        raise ValueError("full_field: `out` was made for other plans or another depth")
+    return out.build(nodes)
+
+
+def _agg_full_bwd_field(agg_func, dA, field, layer, dH, dSelf, argmax, Hprev, ws):
+    import ctypes
+    tplan, op = field.tplan, agg_op(agg_func)
+    nl, nprev, n = field.size(layer), field.size(layer - 1), tplan.n_nodes
+
+    def ok(t, rows, dtype=torch.float32):
+        return t.dtype == dtype and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] == rows
+
+    if not ok(dA, nl):
+        raise ValueError("dA must be float32 [n_layer, F] with unit column stride")
+    F = dA.shape[1]
+    if dH is None:
+        dH = torch.empty(nprev, F, dtype=torch.float32, device=dA.device)
+    if not ok(dH, nprev) or dH.shape[1] < F:
+        raise ValueError("dH must be float32 [n_{layer-1}, F]")
+    if dSelf is not None and (not ok(dSelf, nl) or dSelf.shape[1] < F or dSelf.stride(0) != dA.stride(0)):
+        raise ValueError("dSelf must be float32 [n_layer, F] and share dA's leading dimension")
+    if Hprev is not None and (not ok(Hprev, n) or Hprev.shape[1] < F):
+        raise ValueError("Hprev must be float32 [n_nodes, F]")
+    if op == _lib.GS_AGG_MAX and (argmax is None or not ok(argmax, nl, torch.int32) or argmax.shape[1] < F):
+        raise ValueError("MAX needs the forward's argmax: int32 [n_layer, F]")
+    need = int(lib().gs_agg_full_bwd_ws_bytes(tplan.handle, F))
+    if need < 0:
+        check(_lib.GS_EINVAL)
+    if ws is None:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dA.device)
+    d, rp, cl = tplan.device(dA.device)
+    check(lib().gs_agg_full_bwd_field(field.plan.handle, tplan.handle, ctypes.byref(d), field.ref, layer, op, F,
+                                      ptr(rp), ptr(cl), ptr(dA), ptr(dSelf), dA.stride(0), ptr(argmax),
+                                      argmax.stride(0) if argmax is not None else 0, ptr(Hprev),
+                                      Hprev.stride(0) if Hprev is not None else 0, ptr(dH), dH.stride(0), ptr(ws),
+                                      ws.numel() * ws.element_size(), _stream(dA)))
     return dH
 
 

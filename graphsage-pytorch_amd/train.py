@@ -670,6 +670,9 @@ class FullEmbedder:
 
 
 # ------------------------------------------------------- full-batch training
+ReceptiveField = ops.ReceptiveField
+
+
 class FullTrainer:
     """Exact full-batch training over full neighbourhoods: the reference's
     num_sample=None branch (models.py:280-289) put through loss.backward(),
@@ -711,9 +714,14 @@ class FullTrainer:
     graph at H = 128, L = 2, F = 128.  The graph's entry count enters only
     through the plans and the two device CSRs (12 bytes per entry each).
 
-    Single GPU.  Out of scope: restricting the work to the L-hop receptive
-    field of `nodes` (every step computes all N rows), data parallel, and the
-    unsupervised losses."""
+    Mini-batches: without a field every step computes all N rows, whatever
+    len(nodes) is.  field(nodes) finds the L-hop receptive field of the batch
+    on the device (hip_ops.ReceptiveField), and forward_backward / step /
+    embed with `field=` then work on its rows only -- the same function (every
+    row outside the field has a gradient of exactly zero), at a cost that
+    follows the field instead of N.  The workspace keeps its size.
+
+    Single GPU.  Out of scope: data parallel, and the unsupervised losses."""
 
     def __init__(self, graph, features, labels, n_classes, num_layers=2, hidden=128, agg_func="MEAN", gcn=False,
                  lr=0.7, max_norm=5.0, seed=824, weights=None, optimizer="sgd", betas=(0.9, 0.999), eps=1e-8,
@@ -773,6 +781,7 @@ class FullTrainer:
         self._ws_off = (-self._ws.data_ptr()) % 256
         self.cache_agg1 = bool(cache_agg1)
         self._agg1_valid = False
+        self._agg1_field = 0   # build_id of the field whose compact A_1 the buffer holds (0: none)
         self._opt_step = 0
         self.opt_m = self.opt_v = None
         if self._opt_kind == _lib.GS_OPT_ADAM:
@@ -809,8 +818,36 @@ class FullTrainer:
         self._opt_step = int(state["step"])
 
     def invalidate_cache(self):
-        """Recompute layer 1's aggregate on the next step (the feature table changed in place)."""
+        """Recompute layer 1's aggregate on the next step, full or restricted (the feature table changed in
+        place)."""
         self._agg1_valid = False
+        self._agg1_field = 0
+
+    def field(self, nodes, out=None):
+        """The receptive field of `nodes` under this trainer's plans and depth
+        (a hip_ops.ReceptiveField): pass it as `field=` to forward_backward,
+        step or embed together with the same `nodes`.  It holds for any number
+        of steps (it depends on the graph and `nodes` only); `out`: an earlier
+        field of this trainer to rebuild in place for the next mini-batch,
+        which costs a few dozen small launches and one synchronisation."""
+        nodes = self._nodes(nodes)
+        if out is None:
+            out = ops.ReceptiveField(self.plan, self.tplan, self.L, self.device)
+        elif not isinstance(out, ops.ReceptiveField) or out.plan is not self.plan or out.tplan is not self.tplan or \
+                out.n_layers != self.L:
+            raise ValueError("FullTrainer.field: `out` was made for another plan or depth")
+        return out.build(nodes)
+
+    def _check_field(self, field, nodes):
+        """Every refusal of a field, before any launch."""
+        if not isinstance(field, ops.ReceptiveField) or not field.build_id:
+            raise TypeError("FullTrainer: field must be a built ReceptiveField (FullTrainer.field(nodes))")
+        if field.plan is not self.plan or field.tplan is not self.tplan:
+            raise ValueError("FullTrainer: the field was built for another plan (graph, gcn or seg_len)")
+        if field.n_layers != self.L:
+            raise ValueError(f"FullTrainer: the field was built for {field.n_layers} layers, the model has {self.L}")
+        if not field.covers(nodes):
+            raise ValueError("FullTrainer: the field was built for other nodes than those passed")
 
     def _nodes(self, nodes):
         """`nodes` as a device int32 vector of unique ids in [0, N); every check before any launch of the step."""
@@ -840,13 +877,17 @@ class FullTrainer:
             raise ValueError("FullTrainer: duplicate ids in nodes")
         return torch.from_numpy(a.astype(np.int32)).to(self.device)
 
-    def forward_backward(self, nodes, stages=_lib.GS_TF_ALL):
+    def forward_backward(self, nodes, stages=_lib.GS_TF_ALL, field=None):
         """Loss (device scalar, the NLL mean over `nodes`) and the raw,
         unclipped gradients into self.p.grads: one native call that issues
         every launch of the step on the current stream.  `nodes`: unique ids,
         a device int32 vector or a host array.  `stages`: a _lib.GS_TF_* subset,
-        for measurement only."""
+        for measurement only.  `field`: field(nodes), to work on the batch's
+        receptive field only (gs_train_full_field_forward_backward); hidden()
+        then holds valid rows on R_l only."""
         nodes = self._nodes(nodes)
+        if field is not None:
+            return self._field_forward_backward(nodes, stages, field)
         reuse = self.cache_agg1 and self._agg1_valid
         check(lib().gs_train_full_forward_backward(
             self.plan.handle, ctypes.byref(self._dev), self.tplan.handle, ctypes.byref(self._tdev),
@@ -854,7 +895,23 @@ class FullTrainer:
             self._ws.data_ptr() + self._ws_off, self.ws_bytes, _lib.stream_ptr(self.device)))
         if stages & _lib.GS_TF_FORWARD:
             self._agg1_valid = True
+            self._agg1_field = 0   # the buffer holds the N-row A_1 again
         self._last_nodes = nodes  # alive until the stream has run the step
+        return self.loss
+
+    def _field_forward_backward(self, nodes, stages, field):
+        self._check_field(field, nodes)
+        reuse = self.cache_agg1 and self._agg1_field == field.build_id
+        if stages & _lib.GS_TF_FORWARD and not reuse:
+            self._agg1_valid = False  # the compact A_1 overwrites the full path's
+            self._agg1_field = 0
+        check(lib().gs_train_full_field_forward_backward(
+            self.plan.handle, ctypes.byref(self._dev), self.tplan.handle, ctypes.byref(self._tdev),
+            ctypes.byref(self.cfg), field.ref, nodes.data_ptr(), nodes.numel(), int(reuse), int(stages),
+            self.loss.data_ptr(), self._ws.data_ptr() + self._ws_off, self.ws_bytes, _lib.stream_ptr(self.device)))
+        if stages & _lib.GS_TF_FORWARD:
+            self._agg1_field = field.build_id
+        self._last_nodes, self._last_field = nodes, field  # alive until the stream has run the step
         return self.loss
 
     def apply_update(self):
@@ -866,14 +923,16 @@ class FullTrainer:
         else:
             ops.clip_sgd(self.p.group_off, self.p.params, self.p.grads, 1.0, self.max_norm, self.lr, self.clip_ws)
 
-    def step(self, nodes):
-        loss = self.forward_backward(nodes)
+    def step(self, nodes, field=None):
+        loss = self.forward_backward(nodes, field=field)
         self.apply_update()
         return loss
 
     def hidden(self, layer=None, which=0):
         """A view of H_layer (which=0) or A_layer (which=1) as the last
-        forward left it in the workspace ([N, width]; layer None: the last)."""
+        forward left it in the workspace ([N, width]; layer None: the last).
+        After a field step H_layer holds valid rows on R_layer only, and
+        A_layer's first n_layer rows are the compact aggregate in R_layer order."""
         layer = self.L if layer is None else int(layer)
         off = int(lib().gs_train_full_ws_offset(self.plan.handle, self.tplan.handle, ctypes.byref(self.cfg), which,
                                                 layer))
@@ -888,10 +947,20 @@ class FullTrainer:
         raw = self._ws[self._ws_off + off:self._ws_off + off + nbytes]
         return raw.view(dt).view(n, w)
 
-    def embed(self, nodes=None):
+    def embed(self, nodes=None, field=None):
         """[N, hidden] exact embeddings under the current weights (or the rows
         `nodes`): FullEmbedder over this trainer's parameter views, bitwise
-        FullEmbedder(graph, X, tr.weights(), ...).embed()."""
+        FullEmbedder(graph, X, tr.weights(), ...).embed().  `field`:
+        field(nodes) -- the field path's forward stage alone, then the rows
+        `nodes` of H_L (in the order of `nodes`); it overwrites the step's
+        activations in the workspace.  Restricted inference without a trainer
+        is out of scope: FullEmbedder always computes all N rows."""
+        if field is not None:
+            if nodes is None:
+                raise ValueError("FullTrainer.embed: a field goes with its nodes")
+            nodes = self._nodes(nodes)
+            self._field_forward_backward(nodes, _lib.GS_TF_FORWARD, field)
+            return self.hidden().index_select(0, nodes.long())
         if self._embedder is None:
             self._embedder = FullEmbedder(self.graph, self.X, self.weights(), agg_func=self.agg, gcn=self.gcn,
                                           seg_len=self.plan.seg_len)

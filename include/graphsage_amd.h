@@ -976,6 +976,91 @@ int gs_train_full_forward_backward(const gs_full_plan* plan, const gs_full_plan_
                                    int32_t reuse_agg1, int32_t stages, float* loss,
                                    void* ws, int64_t ws_bytes, void* stream);
 
+/* ------------------------------------- the receptive field of a mini-batch
+ * Exact training restricted to the rows a loss over `nodes` can reach:
+ *   R_L = nodes,  R_{l-1} = R_l U N_eff(R_l)      (N_eff: the plan's effective
+ *   neighbourhood: a row's own id skipped; gcn's own row is in R_l already)
+ * Layer l needs H_l and A_l on R_l only and reads H_{l-1} on R_{l-1} only; every
+ * other row has a gradient of exactly zero, so the restricted step is the same
+ * function as gs_train_full_forward_backward.
+ *
+ * gs_full_field_build finds the field on the device, in the caller's buffer
+ * (gs_full_field_bytes bytes, 256-byte aligned, every launch on `stream`, no
+ * host synchronisation).  Per level l = 0..L (array ids below, level = l):
+ *   ROWS   int32 [n_l]   the ids of R_l, ascending
+ *   POS    int32 [N]     id -> index in ROWS, -1 outside R_l
+ * and per layer l = 1..L, in plan order:
+ *   ITEMS / SPLIT      the forward plan's items / split rows whose row is in R_l
+ *   T_ITEMS / T_SPLIT  the transposed plan's items / split rows whose row is in
+ *                      R_{l-1} (the backward gathers into those rows)
+ * Flags are marked from the compacted items of R_l, one wave per (row,
+ * segment); every list is compacted in order by three launches (per-block
+ * counts, a scan of the block counts, a scatter): deterministic, and no block
+ * waits on another.  rebuild != 0: buf holds an earlier field of the same
+ * plans and n_layers, whose POS maps are reset by walking its ROWS; rebuild ==
+ * 0 clears them (O(N) ints).  nodes: n_nodes unique device ids in [0, N) (an
+ * id outside the range is ignored by the kernels).
+ *
+ * gs_full_field_counts is the one host synchronisation: it copies the counts
+ * to f->counts and waits for `stream`.  counts[l] = n_l for l = 0..L, and
+ * counts[GS_FF_LAYER0 + 4 (l - 1) + k] for layer l: k = 0 items, 1 split rows,
+ * 2 transposed items, 3 transposed split rows. */
+enum { GS_FF_LAYER0 = GS_MAX_HOPS + 1, GS_FF_NCOUNTS = GS_MAX_HOPS + 1 + 4 * GS_MAX_HOPS };
+enum { GS_FF_ROWS = 0, GS_FF_POS, GS_FF_ITEMS, GS_FF_SPLIT, GS_FF_T_ITEMS, GS_FF_T_SPLIT };
+typedef struct {
+    int32_t n_layers, pad_;
+    void* buf;
+    int64_t buf_bytes;
+    int64_t counts[GS_FF_NCOUNTS];   /* host copy (gs_full_field_counts) */
+} gs_full_field;
+int64_t gs_full_field_bytes(const gs_full_plan* plan, const gs_full_plan* tplan, int32_t n_layers);
+/* Byte offset into buf of an array above (level: 0..L for ROWS / POS, 1..L otherwise); -1 on error. */
+int64_t gs_full_field_offset(const gs_full_plan* plan, const gs_full_plan* tplan, int32_t n_layers,
+                             int32_t which, int32_t level);
+int gs_full_field_build(const gs_full_plan* plan, const gs_full_plan_dev* dev,
+                        const gs_full_plan* tplan, const gs_full_plan_dev* tdev,
+                        const int64_t* row_ptr, const int32_t* col,
+                        const int32_t* nodes, int64_t n_nodes, int32_t rebuild,
+                        gs_full_field* f, void* stream);
+int gs_full_field_counts(const gs_full_plan* plan, const gs_full_plan* tplan, gs_full_field* f, void* stream);
+
+/* gs_agg_full / gs_agg_full_argmax over the rows of R_layer: the field's items
+ * and split rows, row v written to row POS_layer[v] of a compact [n_layer, F]
+ * out (and argmax, which still holds global source ids).  Each row sees the
+ * same segments in the same combine order: bitwise the unrestricted row.
+ * argmax == NULL: no argmax.  ws: as the unrestricted call over all rows. */
+int gs_agg_full_field(const gs_full_plan* plan, const gs_full_plan_dev* dev, const gs_full_plan* tplan,
+                      const gs_full_field* f, int32_t layer, gs_agg op, gs_dtype dt,
+                      const void* X, int64_t ldx, int64_t F, const int64_t* row_ptr, const int32_t* col,
+                      void* out, int64_t ldo, int32_t* argmax, int64_t lda,
+                      void* ws, int64_t ws_bytes, void* stream);
+/* gs_agg_full_bwd of layer `layer` into the rows u of R_{layer-1}: the sum runs
+ * over v in T(u) with POS_layer[v] >= 0 and reads dA[POS_layer[v]], count[v] and
+ * argmax[POS_layer[v]]; dSelf[POS_layer[u]] is added only where u is in R_layer;
+ * Hprev is the N-row table (row u); dH is compact, row POS_{layer-1}[u] of
+ * [n_{layer-1}, F], each row written in full. */
+int gs_agg_full_bwd_field(const gs_full_plan* plan, const gs_full_plan* tplan, const gs_full_plan_dev* tdev,
+                          const gs_full_field* f, int32_t layer, gs_agg op, int64_t F,
+                          const int64_t* t_row_ptr, const int32_t* t_col, const float* dA,
+                          const float* dSelf, int64_t ldd, const int32_t* argmax, int64_t lda,
+                          const float* Hprev, int64_t ldh, float* dH, int64_t ldo,
+                          void* ws, int64_t ws_bytes, void* stream);
+
+/* gs_train_full_forward_backward restricted to the field of `nodes` (f built
+ * for these nodes, plans and cfg->n_layers; counts read back).  Same config,
+ * workspace and stages.  The H_l tables stay N-row and indexed by global id
+ * (only rows of R_l are written, only rows of R_{l-1} are read at layer l);
+ * A_l, argmax_l, dH_l, dSelf and dA are compact in R_l order; the GEMMs run
+ * over n_l rows with the self rows indexed by ROWS_l.  No launch does work
+ * proportional to N x width.  reuse_agg1: the compact A_1 in ws was written by
+ * a field step over this very field. */
+int gs_train_full_field_forward_backward(const gs_full_plan* plan, const gs_full_plan_dev* dev,
+                                         const gs_full_plan* tplan, const gs_full_plan_dev* tdev,
+                                         const gs_train_full_config* cfg, const gs_full_field* f,
+                                         const int32_t* nodes, int64_t n_nodes,
+                                         int32_t reuse_agg1, int32_t stages, float* loss,
+                                         void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
