@@ -45,3 +45,12 @@ struct Error : std::runtime_error {
         return GS_EINVAL;                                 \
     }                                                     \
     return GS_OK;
+
+// The same guard for an entry point that returns a byte count or offset: -1 after set_error.
+#define GS_BYTES_BEGIN try {
+#define GS_BYTES_END                                      \
+    }                                                     \
+    catch (const std::exception& e) {                     \
+        ::gs::set_error(e.what());                        \
+        return -1;                                        \
+    }

@@ -152,27 +152,14 @@ __global__ __launch_bounds__(kBlock) void agg_full_combine_kernel(const T* __res
     }
 }
 
-template <int OP, typename T, int VEC, int G>
-static void launch_full(const T* X, T* out, const FullArgs& a, hipStream_t st) {
-    constexpr int per = kBlock / G;
-    const dim3 gi((a.n_items + per - 1) / per), gc((a.n_split + per - 1) / per);
-    if (a.pos) {  // a field's rows: the same walk and combine, the output row from the map
-        if (a.n_items > 0) agg_full_kernel<OP, T, VEC, G, true><<<gi, kBlock, 0, st>>>(X, out, a);
-        if (a.n_split > 0) agg_full_combine_kernel<OP, T, VEC, G, true><<<gc, kBlock, 0, st>>>(X, out, a);
-        return;
-    }
-    if (a.n_items > 0) agg_full_kernel<OP, T, VEC, G, false><<<gi, kBlock, 0, st>>>(X, out, a);
-    if (a.n_split > 0) agg_full_combine_kernel<OP, T, VEC, G, false><<<gc, kBlock, 0, st>>>(X, out, a);
-}
-
 template <int OP, typename T>
 static void launch_full_t(bool vec, const T* X, T* out, const FullArgs& a, hipStream_t st) {
-    constexpr int V = sizeof(T) == 4 ? 4 : 8;
-    if (!vec) return launch_full<OP, T, 1, 64>(X, out, a, st);
-    const int G = pick_group(a.F, V);
-    if (G == 16) launch_full<OP, T, V, 16>(X, out, a, st);
-    else if (G == 32) launch_full<OP, T, V, 32>(X, out, a, st);
-    else launch_full<OP, T, V, 64>(X, out, a, st);
+    with_group<sizeof(T) == 4 ? 4 : 8>(vec, a.F, [&](auto vc, auto gc) {
+        constexpr int VEC = decltype(vc)::value, G = decltype(gc)::value;
+        launch_walk_combine<G>(a.pos != nullptr, a.n_items, a.n_split, st, agg_full_kernel<OP, T, VEC, G, true>,
+                               agg_full_combine_kernel<OP, T, VEC, G, true>, agg_full_kernel<OP, T, VEC, G, false>,
+                               agg_full_combine_kernel<OP, T, VEC, G, false>, X, out, a);
+    });
 }
 
 static void check_window(const FullPlan& p, int64_t row0, int64_t n_rows) {
@@ -186,49 +173,50 @@ int64_t agg_full_ws_need(const FullPlan& p, int64_t F, int64_t row0, int64_t n_r
     return (p.slot_ptr[row0 + n_rows] - p.slot_ptr[row0]) * F * static_cast<int64_t>(sizeof(float));
 }
 
+FullArgs full_args(const FullPlan& p, const gs_full_plan_dev& d, const int64_t* row_ptr, const int32_t* col,
+                   int64_t row0, int64_t n_rows, int64_t F, int64_t ldx, int64_t ldo, void* ws, const FieldLayer* fl) {
+    GS_REQUIRE(!fl || (row0 == 0 && n_rows == p.n), GS_EINVAL, "a field covers the whole plan");
+    check_window(p, row0, n_rows);
+    GS_REQUIRE(row_ptr && col && d.items && d.slot_ptr && d.count && d.self_loop, GS_EINVAL, "NULL device pointer");
+    FullArgs a;
+    a.n_split = fl ? static_cast<int>(fl->n_split) : static_cast<int>(p.split_ptr[row0 + n_rows] - p.split_ptr[row0]);
+    GS_REQUIRE(a.n_split == 0 || d.split_rows, GS_EINVAL, "NULL split_rows");
+    a.ldx = ldx;
+    a.ldo = ldo;
+    a.row_ptr = row_ptr;
+    a.col = col;
+    a.items = fl ? fl->items : d.items + 2 * p.item_ptr[row0];
+    a.slot_ptr = d.slot_ptr;
+    a.split_rows = fl ? fl->split : a.n_split ? d.split_rows + p.split_ptr[row0] : nullptr;
+    a.cnt = d.count;
+    a.self_loop = d.self_loop;
+    a.pos = fl ? fl->pos : nullptr;
+    a.part = static_cast<float*>(ws);
+    a.slot0 = p.slot_ptr[row0];
+    a.seg_len = std::min<int64_t>(p.seg_len, (int64_t(1) << 31) - 1);
+    a.F = static_cast<int>(F);
+    a.n_items = static_cast<int>(fl ? fl->n_items : p.item_ptr[row0 + n_rows] - p.item_ptr[row0]);
+    a.row0 = static_cast<int>(row0);
+    a.gcn = p.gcn;
+    return a;
+}
+
 void agg_full_launch(const FullPlan& p, const gs_full_plan_dev& d, gs_agg op, gs_dtype dt, const void* X, int64_t ldx,
                      int64_t F, const int64_t* row_ptr, const int32_t* col, int64_t row0, int64_t n_rows, void* out,
                      int64_t ldo, void* ws, int64_t ws_bytes, hipStream_t st, const FieldLayer* fl) {
-    GS_REQUIRE(!fl || (row0 == 0 && n_rows == p.n), GS_EINVAL, "a field covers the whole plan");
     GS_REQUIRE(op == GS_AGG_MEAN || op == GS_AGG_MAX, GS_EINVAL, "agg_func must be MEAN or MAX");
     GS_REQUIRE(dt == GS_F32 || dt == GS_BF16, GS_EINVAL, "dtype must be f32 or bf16");
     const int64_t need = agg_full_ws_need(p, F, row0, n_rows);
     GS_REQUIRE(ldx >= F && ldo >= F, GS_EINVAL, "leading dimension smaller than F");
     if (n_rows == 0) return;
-    GS_REQUIRE(X && row_ptr && col && out && d.items && d.slot_ptr && d.count && d.self_loop, GS_EINVAL,
-               "NULL device pointer");
+    GS_REQUIRE(X && out, GS_EINVAL, "NULL device pointer");
+    const FullArgs a = full_args(p, d, row_ptr, col, row0, n_rows, F, ldx, ldo, ws, fl);
     if (op == GS_AGG_MAX && full_plan_empty_in(p, row0, n_rows) > 0)
         fail(GS_EEMPTY, "gs_agg_full: MAX aggregation over an empty neighbourhood (reference: models.py:321-325)");
-    FullArgs a;
-    a.n_split = fl ? static_cast<int>(fl->n_split) : static_cast<int>(p.split_ptr[row0 + n_rows] - p.split_ptr[row0]);
     GS_REQUIRE(need == 0 || (ws && ws_bytes >= need), GS_EINVAL, "workspace smaller than gs_agg_full_ws_bytes");
-    GS_REQUIRE(a.n_split == 0 || d.split_rows, GS_EINVAL, "NULL split_rows");
     const int V = dt == GS_F32 ? 4 : 8;
     const bool vec = F % V == 0 && ldx % V == 0 && ldo % V == 0 && aligned16(X) && aligned16(out) &&
                      (need == 0 || aligned16(ws));
-    a.ldx = ldx;
-    a.ldo = ldo;
-    a.row_ptr = row_ptr;
-    a.col = col;
-    a.items = d.items + 2 * p.item_ptr[row0];
-    a.slot_ptr = d.slot_ptr;
-    a.split_rows = a.n_split ? d.split_rows + p.split_ptr[row0] : nullptr;
-    a.cnt = d.count;
-    a.self_loop = d.self_loop;
-    a.part = static_cast<float*>(ws);
-    a.slot0 = p.slot_ptr[row0];
-    a.seg_len = std::min<int64_t>(p.seg_len, (int64_t(1) << 31) - 1);
-    a.F = static_cast<int>(F);
-    a.n_items = static_cast<int>(p.item_ptr[row0 + n_rows] - p.item_ptr[row0]);
-    a.row0 = static_cast<int>(row0);
-    a.gcn = p.gcn;
-    a.pos = nullptr;
-    if (fl) {
-        a.items = fl->items;
-        a.n_items = static_cast<int>(fl->n_items);
-        a.split_rows = fl->split;
-        a.pos = fl->pos;
-    }
     if (op == GS_AGG_MEAN) {
         if (dt == GS_F32) launch_full_t<GS_AGG_MEAN, float>(vec, static_cast<const float*>(X), static_cast<float*>(out), a, st);
         else launch_full_t<GS_AGG_MEAN, bf16_t>(vec, static_cast<const bf16_t*>(X), static_cast<bf16_t*>(out), a, st);
@@ -244,13 +232,10 @@ void agg_full_launch(const FullPlan& p, const gs_full_plan_dev& d, gs_agg op, gs
 extern "C" {
 
 int64_t gs_agg_full_ws_bytes(const gs_full_plan* plan, int64_t F, int64_t row0, int64_t n_rows) {
-    try {
-        if (!plan) return -1;
-        return gs::agg_full_ws_need(*reinterpret_cast<const gs::FullPlan*>(plan), F, row0, n_rows);
-    } catch (const std::exception& e) {
-        gs::set_error(e.what());
-        return -1;
-    }
+    GS_BYTES_BEGIN
+    if (!plan) return -1;
+    return gs::agg_full_ws_need(*reinterpret_cast<const gs::FullPlan*>(plan), F, row0, n_rows);
+    GS_BYTES_END
 }
 
 int gs_agg_full(const gs_full_plan* plan, const gs_full_plan_dev* dev, gs_agg op, gs_dtype dt, const void* X,

@@ -2,10 +2,17 @@
 // Internal launcher of the full-neighbourhood aggregate (agg_full.hip), shared
 // with the layer-wise driver (infer_full.hip).  Throws gs::Error.
 #include "../host/full_plan.hpp"
+#include "agg_dev.hpp"
 #include "full_field.hpp"
 #include "kcommon.hpp"
 
+#include <type_traits>
+
 namespace gs {
+
+// Every offset into a layer-wise driver's workspace (infer_full.hip, train_full.hip) is a multiple of kAlign.
+constexpr int64_t kAlign = 256;
+inline int64_t round_up(int64_t b) { return (b + kAlign - 1) / kAlign * kAlign; }
 
 // fp32 partial rows of a split row's segments, and the kernels' arguments (agg_full.hip, agg_full_bwd.hip)
 template <int VEC>
@@ -48,6 +55,36 @@ struct FullArgs {
     int F, n_items, n_split, row0, gcn;
 };
 
+// The arguments of the window [row0, row0 + n_rows), n_rows > 0, or of a field's rows (`fl`, below), after the
+// checks both forward launchers share: the window, the field, the plan's and the CSR's pointers, the split rows.
+FullArgs full_args(const FullPlan& p, const gs_full_plan_dev& d, const int64_t* row_ptr, const int32_t* col,
+                   int64_t row0, int64_t n_rows, int64_t F, int64_t ldx, int64_t ldo, void* ws, const FieldLayer* fl);
+
+// fn(VEC, G) as integral constants: one element per lane and 64 lanes unless `vec`, else V elements per lane and
+// pick_group's 16, 32 or 64 lanes for a row of F.
+template <int V, typename Fn>
+void with_group(bool vec, int F, Fn fn) {
+    using std::integral_constant;
+    if (!vec) return fn(integral_constant<int, 1>{}, integral_constant<int, 64>{});
+    const int G = pick_group(F, V);
+    if (G == 16) fn(integral_constant<int, V>{}, integral_constant<int, 16>{});
+    else if (G == 32) fn(integral_constant<int, V>{}, integral_constant<int, 32>{});
+    else fn(integral_constant<int, V>{}, integral_constant<int, 64>{});
+}
+
+// An aggregate's two launches: the walk, one lane group of G per item, then the combine, one per split row; either
+// is skipped when it has nothing to do.  `map`: a field's rows -- the same walk and combine, the MAP pair.
+template <int G, typename Walk, typename Combine, typename... Args>
+void launch_walk_combine(bool map, int n_items, int n_split, hipStream_t st, Walk walk_map, Combine combine_map,
+                         Walk walk, Combine combine, const Args&... args) {
+    constexpr int per = kBlock / G;
+    if (map) {
+        walk = walk_map;
+        combine = combine_map;
+    }
+    if (n_items > 0) walk<<<dim3((n_items + per - 1) / per), kBlock, 0, st>>>(args...);
+    if (n_split > 0) combine<<<dim3((n_split + per - 1) / per), kBlock, 0, st>>>(args...);
+}
 
 // Bytes of fp32 partials the window [row0, row0 + n_rows) needs at width F.
 int64_t agg_full_ws_need(const FullPlan& p, int64_t F, int64_t row0, int64_t n_rows);

@@ -213,19 +213,6 @@ __global__ __launch_bounds__(kBlock) void agg_full_argmax_combine_kernel(const f
     }
 }
 
-template <int VEC, int G>
-void launch_argmax(const float* X, float* out, const FullArgs& a, const ArgmaxOut& o, hipStream_t st) {
-    constexpr int per = kBlock / G;
-    const dim3 gi((a.n_items + per - 1) / per), gc((a.n_split + per - 1) / per);
-    if (a.pos) {  // a field's rows
-        if (a.n_items > 0) agg_full_argmax_kernel<VEC, G, true><<<gi, kBlock, 0, st>>>(X, out, a, o);
-        if (a.n_split > 0) agg_full_argmax_combine_kernel<VEC, G, true><<<gc, kBlock, 0, st>>>(X, out, a, o);
-        return;
-    }
-    if (a.n_items > 0) agg_full_argmax_kernel<VEC, G, false><<<gi, kBlock, 0, st>>>(X, out, a, o);
-    if (a.n_split > 0) agg_full_argmax_combine_kernel<VEC, G, false><<<gc, kBlock, 0, st>>>(X, out, a, o);
-}
-
 // ------------------------------------------------------------------ backward
 struct BwdArgs {
     const int64_t* row_ptr;  // the transposed CSR
@@ -378,26 +365,14 @@ __global__ __launch_bounds__(kBlock) void agg_full_bwd_combine_kernel(BwdArgs a)
     }
 }
 
-template <int OP, int VEC, int G>
-void launch_bwd(const BwdArgs& a, hipStream_t st) {
-    constexpr int per = kBlock / G;
-    const dim3 gi((a.n_items + per - 1) / per), gc((a.n_split + per - 1) / per);
-    if (a.pos) {  // a field's rows
-        if (a.n_items > 0) agg_full_bwd_kernel<OP, VEC, G, true><<<gi, kBlock, 0, st>>>(a);
-        if (a.n_split > 0) agg_full_bwd_combine_kernel<VEC, G, true><<<gc, kBlock, 0, st>>>(a);
-        return;
-    }
-    if (a.n_items > 0) agg_full_bwd_kernel<OP, VEC, G, false><<<gi, kBlock, 0, st>>>(a);
-    if (a.n_split > 0) agg_full_bwd_combine_kernel<VEC, G, false><<<gc, kBlock, 0, st>>>(a);
-}
-
 template <int OP>
 void launch_bwd_t(bool vec, const BwdArgs& a, hipStream_t st) {
-    if (!vec) return launch_bwd<OP, 1, 64>(a, st);
-    const int G = pick_group(a.F, 4);
-    if (G == 16) launch_bwd<OP, 4, 16>(a, st);
-    else if (G == 32) launch_bwd<OP, 4, 32>(a, st);
-    else launch_bwd<OP, 4, 64>(a, st);
+    with_group<4>(vec, a.F, [&](auto vc, auto gc) {
+        constexpr int VEC = decltype(vc)::value, G = decltype(gc)::value;
+        launch_walk_combine<G>(a.pos != nullptr, a.n_items, a.n_split, st, agg_full_bwd_kernel<OP, VEC, G, true>,
+                               agg_full_bwd_combine_kernel<VEC, G, true>, agg_full_bwd_kernel<OP, VEC, G, false>,
+                               agg_full_bwd_combine_kernel<VEC, G, false>, a);
+    });
 }
 
 }  // namespace
@@ -410,60 +385,31 @@ void agg_full_argmax_launch(const FullPlan& p, const gs_full_plan_dev& d, gs_dty
                             int64_t F, const int64_t* row_ptr, const int32_t* col, int64_t row0, int64_t n_rows,
                             void* out, int64_t ldo, int32_t* argmax, int64_t lda, void* ws, int64_t ws_bytes,
                             hipStream_t st, const FieldLayer* fl) {
-    GS_REQUIRE(!fl || (row0 == 0 && n_rows == p.n), GS_EINVAL, "a field covers the whole plan");
     GS_REQUIRE(dt == GS_F32, GS_EINVAL, "gs_agg_full_argmax: fp32 rows only (a bf16 table's aggregate has no backward)");
     GS_REQUIRE(!p.transposed, GS_EINVAL, "gs_agg_full_argmax: a forward plan expected");
     const int64_t need = agg_full_argmax_ws_need(p, F, row0, n_rows);
     GS_REQUIRE(ldx >= F && ldo >= F && lda >= F, GS_EINVAL, "leading dimension smaller than F");
     if (n_rows == 0) return;
-    GS_REQUIRE(X && row_ptr && col && out && argmax && d.items && d.slot_ptr && d.count && d.self_loop, GS_EINVAL,
-               "NULL device pointer");
+    GS_REQUIRE(X && out && argmax, GS_EINVAL, "NULL device pointer");
+    const FullArgs a = full_args(p, d, row_ptr, col, row0, n_rows, F, ldx, ldo, ws, fl);
     if (full_plan_empty_in(p, row0, n_rows) > 0)
         fail(GS_EEMPTY, "gs_agg_full_argmax: MAX aggregation over an empty neighbourhood (reference: models.py:321-325)");
-    FullArgs a;
-    a.n_split = fl ? static_cast<int>(fl->n_split) : static_cast<int>(p.split_ptr[row0 + n_rows] - p.split_ptr[row0]);
     GS_REQUIRE(need == 0 || (ws && ws_bytes >= need), GS_EINVAL,
                "workspace smaller than gs_agg_full_argmax_ws_bytes");
-    GS_REQUIRE(a.n_split == 0 || d.split_rows, GS_EINVAL, "NULL split_rows");
     const bool vec = F % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0 && lda % 4 == 0 && aligned16(X) && aligned16(out) &&
                      aligned16(argmax) && (need == 0 || aligned16(ws));
-    a.ldx = ldx;
-    a.ldo = ldo;
-    a.row_ptr = row_ptr;
-    a.col = col;
-    a.items = d.items + 2 * p.item_ptr[row0];
-    a.slot_ptr = d.slot_ptr;
-    a.split_rows = a.n_split ? d.split_rows + p.split_ptr[row0] : nullptr;
-    a.cnt = d.count;
-    a.self_loop = d.self_loop;
-    a.part = static_cast<float*>(ws);
-    a.slot0 = p.slot_ptr[row0];
-    a.seg_len = std::min<int64_t>(p.seg_len, (int64_t(1) << 31) - 1);
-    a.F = static_cast<int>(F);
-    a.n_items = static_cast<int>(p.item_ptr[row0 + n_rows] - p.item_ptr[row0]);
-    a.row0 = static_cast<int>(row0);
-    a.gcn = p.gcn;
-    a.pos = nullptr;
-    if (fl) {
-        a.items = fl->items;
-        a.n_items = static_cast<int>(fl->n_items);
-        a.split_rows = fl->split;
-        a.pos = fl->pos;
-    }
     ArgmaxOut o;
     o.am = argmax;
     o.lda = lda;
     o.part_ids = reinterpret_cast<int*>(static_cast<char*>(ws) + need / 2);  // F % 4 == 0 keeps it 16-byte aligned
     const float* Xf = static_cast<const float*>(X);
     float* of = static_cast<float*>(out);
-    if (!vec) {
-        launch_argmax<1, 64>(Xf, of, a, o, st);
-    } else {
-        const int G = pick_group(a.F, 4);
-        if (G == 16) launch_argmax<4, 16>(Xf, of, a, o, st);
-        else if (G == 32) launch_argmax<4, 32>(Xf, of, a, o, st);
-        else launch_argmax<4, 64>(Xf, of, a, o, st);
-    }
+    with_group<4>(vec, a.F, [&](auto vc, auto gc) {
+        constexpr int VEC = decltype(vc)::value, G = decltype(gc)::value;
+        launch_walk_combine<G>(a.pos != nullptr, a.n_items, a.n_split, st, agg_full_argmax_kernel<VEC, G, true>,
+                               agg_full_argmax_combine_kernel<VEC, G, true>, agg_full_argmax_kernel<VEC, G, false>,
+                               agg_full_argmax_combine_kernel<VEC, G, false>, Xf, of, a, o);
+    });
     check_launch("gs_agg_full_argmax");
 }
 
@@ -530,13 +476,10 @@ void agg_full_bwd_launch(const FullPlan& tp, const gs_full_plan_dev& td, gs_agg 
 extern "C" {
 
 int64_t gs_agg_full_argmax_ws_bytes(const gs_full_plan* plan, int64_t F, int64_t row0, int64_t n_rows) {
-    try {
-        if (!plan) return -1;
-        return gs::agg_full_argmax_ws_need(*reinterpret_cast<const gs::FullPlan*>(plan), F, row0, n_rows);
-    } catch (const std::exception& e) {
-        gs::set_error(e.what());
-        return -1;
-    }
+    GS_BYTES_BEGIN
+    if (!plan) return -1;
+    return gs::agg_full_argmax_ws_need(*reinterpret_cast<const gs::FullPlan*>(plan), F, row0, n_rows);
+    GS_BYTES_END
 }
 
 int gs_agg_full_argmax(const gs_full_plan* plan, const gs_full_plan_dev* dev, gs_dtype dt, const void* X, int64_t ldx,
@@ -550,13 +493,10 @@ int gs_agg_full_argmax(const gs_full_plan* plan, const gs_full_plan_dev* dev, gs
 }
 
 int64_t gs_agg_full_bwd_ws_bytes(const gs_full_plan* tplan, int64_t F) {
-    try {
-        if (!tplan) return -1;
-        return gs::agg_full_bwd_ws_need(*reinterpret_cast<const gs::FullPlan*>(tplan), F);
-    } catch (const std::exception& e) {
-        gs::set_error(e.what());
-        return -1;
-    }
+    GS_BYTES_BEGIN
+    if (!tplan) return -1;
+    return gs::agg_full_bwd_ws_need(*reinterpret_cast<const gs::FullPlan*>(tplan), F);
+    GS_BYTES_END
 }
 
 int gs_agg_full_bwd(const gs_full_plan* tplan, const gs_full_plan_dev* tdev, gs_agg op, int64_t F,

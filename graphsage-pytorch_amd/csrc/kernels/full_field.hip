@@ -346,35 +346,29 @@ static void field_build(const FullPlan& p, const gs_full_plan_dev& d, const Full
 extern "C" {
 
 int64_t gs_full_field_bytes(const gs_full_plan* plan, const gs_full_plan* tplan, int32_t n_layers) {
-    try {
-        if (!plan || !tplan) return -1;
-        return gs::field_layout(*reinterpret_cast<const gs::FullPlan*>(plan),
-                                *reinterpret_cast<const gs::FullPlan*>(tplan), n_layers).total;
-    } catch (const std::exception& e) {
-        gs::set_error(e.what());
-        return -1;
-    }
+    GS_BYTES_BEGIN
+    if (!plan || !tplan) return -1;
+    return gs::field_layout(*reinterpret_cast<const gs::FullPlan*>(plan),
+                            *reinterpret_cast<const gs::FullPlan*>(tplan), n_layers).total;
+    GS_BYTES_END
 }
 
 int64_t gs_full_field_offset(const gs_full_plan* plan, const gs_full_plan* tplan, int32_t n_layers, int32_t which,
                              int32_t level) {
-    try {
-        if (!plan || !tplan || level < 0 || level > n_layers) return -1;
-        const gs::FieldLayout lo = gs::field_layout(*reinterpret_cast<const gs::FullPlan*>(plan),
-                                                    *reinterpret_cast<const gs::FullPlan*>(tplan), n_layers);
-        switch (which) {
-            case GS_FF_ROWS: return lo.rows[level];
-            case GS_FF_POS: return lo.pos[level];
-            case GS_FF_ITEMS: return lo.items[level];
-            case GS_FF_SPLIT: return lo.split[level];
-            case GS_FF_T_ITEMS: return lo.t_items[level];
-            case GS_FF_T_SPLIT: return lo.t_split[level];
-            default: return -1;
-        }
-    } catch (const std::exception& e) {
-        gs::set_error(e.what());
-        return -1;
+    GS_BYTES_BEGIN
+    if (!plan || !tplan || level < 0 || level > n_layers) return -1;
+    const gs::FieldLayout lo = gs::field_layout(*reinterpret_cast<const gs::FullPlan*>(plan),
+                                                *reinterpret_cast<const gs::FullPlan*>(tplan), n_layers);
+    switch (which) {
+        case GS_FF_ROWS: return lo.rows[level];
+        case GS_FF_POS: return lo.pos[level];
+        case GS_FF_ITEMS: return lo.items[level];
+        case GS_FF_SPLIT: return lo.split[level];
+        case GS_FF_T_ITEMS: return lo.t_items[level];
+        case GS_FF_T_SPLIT: return lo.t_split[level];
+        default: return -1;
     }
+    GS_BYTES_END
 }
 
 int gs_full_field_build(const gs_full_plan* plan, const gs_full_plan_dev* dev, const gs_full_plan* tplan,

@@ -16,9 +16,6 @@ namespace gs {
 
 namespace {
 
-constexpr int64_t kAlign = 256;
-int64_t round_up(int64_t b) { return (b + kAlign - 1) / kAlign * kAlign; }
-
 struct FullLayout {
     int64_t chunk = 0, w1lp = -1, h[2] = {-1, -1}, a = 0, part = 0, part_bytes = 0, total = 0;
 };
@@ -101,13 +98,10 @@ void infer_full_run(const FullPlan& p, const gs_full_plan_dev& d, const gs_infer
 extern "C" {
 
 int64_t gs_infer_full_ws_bytes(const gs_full_plan* plan, const gs_infer_full_config* cfg) {
-    try {
-        if (!plan || !cfg) return -1;
-        return gs::layout_of(*reinterpret_cast<const gs::FullPlan*>(plan), *cfg).total;
-    } catch (const std::exception& e) {
-        gs::set_error(e.what());
-        return -1;
-    }
+    GS_BYTES_BEGIN
+    if (!plan || !cfg) return -1;
+    return gs::layout_of(*reinterpret_cast<const gs::FullPlan*>(plan), *cfg).total;
+    GS_BYTES_END
 }
 
 int gs_infer_full(const gs_full_plan* plan, const gs_full_plan_dev* dev, const gs_infer_full_config* cfg, float* out,

@@ -7,6 +7,12 @@
 // launch goes to the caller's stream and nothing is allocated: all buffers
 // live in the caller's workspace (layout_of).
 //
+// One driver, train_full_run, runs the step over all N rows and restricted to
+// the receptive field of `nodes` (full_field.hip): the checks, the parameter
+// offsets, the forward loop, the head and the backward loop are written once,
+// and what the restricted step does differently is data (LayerRows) and two
+// `if (f)` blocks, described in front of the driver.
+//
 // Row counts: the weight-gradient launcher cuts N rows into slabs of at most
 // 2048 rows (dw_rows_per_split) summed in slab order, its and the
 // input-gradient launcher's row offsets are 64-bit and their grids
@@ -20,9 +26,6 @@
 namespace gs {
 
 namespace {
-
-constexpr int64_t kAlign = 256;
-int64_t round_up(int64_t b) { return (b + kAlign - 1) / kAlign * kAlign; }
 
 struct TrainLayout {
     int64_t w1lp = -1;
@@ -101,91 +104,6 @@ __global__ __launch_bounds__(256) void rows_by_id_kernel(float* __restrict__ Hs,
     else *e = *hs;
 }
 
-void ok(int rc) {
-    if (rc != GS_OK) fail(rc, gs_last_error());
-}
-
-}  // namespace
-
-void train_full_run(const FullPlan& p, const gs_full_plan_dev& d, const FullPlan& tp, const gs_full_plan_dev& td,
-                    const gs_train_full_config& c, const int32_t* nodes, int64_t B, int reuse_agg1, int stages,
-                    float* loss, void* ws, int64_t ws_bytes, hipStream_t st) {
-    const TrainLayout lo = layout_of(p, tp, c);
-    const int64_t n = p.n, H = c.hidden, L = c.n_layers, C = c.n_classes, m = p.gcn ? 1 : 2;
-    GS_REQUIRE(c.X && c.row_ptr && c.col && c.t_row_ptr && c.t_col && c.labels && c.params && c.grads && loss,
-               GS_EINVAL, "NULL pointer");
-    GS_REQUIRE(nodes && B >= 1 && B <= c.max_nodes, GS_EINVAL, "nodes: 1 to max_nodes ids");
-    GS_REQUIRE(stages >= 1 && stages <= GS_TF_ALL, GS_EINVAL, "bad stages");
-    GS_REQUIRE(ws && ws_bytes >= lo.total && (reinterpret_cast<uintptr_t>(ws) & (kAlign - 1)) == 0, GS_EINVAL,
-               "workspace smaller than gs_train_full_ws_bytes or not 256-byte aligned");
-    GS_REQUIRE(aligned16(c.params) && aligned16(c.grads), GS_EINVAL, "params / grads must be 16-byte aligned");
-    if (!p.empty_rows.empty())
-        fail(GS_EEMPTY, "gs_train_full: a node's effective neighbourhood is empty (reference: models.py:313, :321-325)");
-    char* base = static_cast<char*>(ws);
-    const gs_agg op = static_cast<gs_agg>(c.agg);
-    auto fptr = [&](int64_t o) { return reinterpret_cast<float*>(base + o); };
-    // the flat parameter layout: W_1 .. W_L, Wc, bc
-    int64_t woff[GS_MAX_HOPS + 1];
-    woff[0] = 0;
-    for (int l = 1; l <= L; ++l) woff[l] = woff[l - 1] + H * m * in_width(c, l);
-    const int64_t wc_off = woff[L], bc_off = wc_off + C * H;
-
-    if (stages & GS_TF_FORWARD) {
-        if (lo.w1lp >= 0) ok(gs_cast_f32_bf16(c.params, base + lo.w1lp, H * m * c.feat_dim, st));
-        for (int l = 1; l <= L; ++l) {
-            const gs_dtype dt = l == 1 ? static_cast<gs_dtype>(c.feat_dtype) : GS_F32;
-            const char* in = l == 1 ? static_cast<const char*>(c.X) : base + lo.h[l - 2];
-            const int64_t ldin = l == 1 ? c.feat_ld : H, fin = in_width(c, l);
-            if (lo.am[l - 1] >= 0)
-                agg_full_argmax_launch(p, d, dt, in, ldin, fin, c.row_ptr, c.col, 0, n, base + lo.a[l - 1], fin,
-                                       reinterpret_cast<int32_t*>(base + lo.am[l - 1]), fin, base + lo.part,
-                                       lo.part_bytes, st);
-            else if (l > 1 || !reuse_agg1)
-                agg_full_launch(p, d, op, dt, in, ldin, fin, c.row_ptr, c.col, 0, n, base + lo.a[l - 1], fin,
-                                base + lo.part, lo.part_bytes, st);
-            const void* W = (l == 1 && lo.w1lp >= 0) ? static_cast<const void*>(base + lo.w1lp)
-                                                     : static_cast<const void*>(c.params + woff[l - 1]);
-            linear_fwd_launch(dt, n, fin, H, p.gcn ? nullptr : in, ldin, nullptr, base + lo.a[l - 1], fin, W,
-                              fptr(lo.h[l - 1]), H, 1, st);
-        }
-    }
-    float* dh_top = fptr(lo.dh[(L - 1) % 2]);
-    if (stages & GS_TF_HEAD) {
-        const int q = static_cast<int>(H / 4);
-        const unsigned grid = static_cast<unsigned>((B * q + 255) / 256);
-        rows_by_id_kernel<false><<<dim3(grid), 256, 0, st>>>(fptr(lo.h[L - 1]), fptr(lo.e), nodes, B, q);
-        check_launch("gs_train_full(gather)");
-        // dE masked by relu'(H_L): the rows of dZ_L, every other row of it zero
-        ok(gs_cls_nll_fwd_bwd(B, H, C, fptr(lo.e), c.params + wc_off, c.params + bc_off, c.labels, nodes, 1, loss,
-                              fptr(lo.de), c.grads + wc_off, c.grads + bc_off, fptr(lo.cls), st));
-        GS_REQUIRE(hipMemsetAsync(dh_top, 0, n * H * 4, st) == hipSuccess, GS_EHIP, "memset failed");
-        rows_by_id_kernel<true><<<dim3(grid), 256, 0, st>>>(dh_top, fptr(lo.de), nodes, B, q);
-        check_launch("gs_train_full(scatter)");
-    }
-    if (stages & GS_TF_BACKWARD) {
-        for (int l = static_cast<int>(L); l >= 1; --l) {
-            const gs_dtype dt = l == 1 ? static_cast<gs_dtype>(c.feat_dtype) : GS_F32;
-            const char* in = l == 1 ? static_cast<const char*>(c.X) : base + lo.h[l - 2];
-            const int64_t ldin = l == 1 ? c.feat_ld : H, fin = in_width(c, l);
-            const float* dz = fptr(lo.dh[(l - 1) % 2]);  // dH_l, already masked by relu'(H_l)
-            float* dW = c.grads + woff[l - 1];
-            // gs_sage_linear_bwd_weight's two launches: row slabs, then their sum in slab order
-            const int S = linear_dw_slabs(dt, n, fin, H, p.gcn ? nullptr : in, ldin, nullptr, base + lo.a[l - 1], fin,
-                                          dz, nullptr, H, 0, dW, base + lo.slab, lo.slab_bytes, st, -1,
-                                          n >= 512 ? kDw1Phases : 1);
-            if (S > 1) sum_slabs_launch(fptr(lo.slab), S, H * m * fin, dW, nullptr, st);
-            if (l == 1) break;  // the feature table has no gradient
-            float* dself = p.gcn ? nullptr : fptr(lo.dself);
-            ok(gs_sage_linear_bwd_input(n, H, H, dz, nullptr, H, 0, c.params + woff[l - 1], dself, fptr(lo.da), H, st));
-            agg_full_bwd_launch(tp, td, op, H, c.t_row_ptr, c.t_col, fptr(lo.da), dself, H,
-                                lo.am[l - 1] >= 0 ? reinterpret_cast<const int32_t*>(base + lo.am[l - 1]) : nullptr, H,
-                                fptr(lo.h[l - 2]), fptr(lo.dh[(l - 2) % 2]), H, base + lo.part, lo.part_bytes, st);
-        }
-    }
-}
-
-namespace {
-
 // D[map[nodes[i]]] = E[i]: the loss head's rows into the compact dH_L (map: the field's pos_L).
 __global__ __launch_bounds__(256) void rows_by_map_kernel(float* __restrict__ D, const float* __restrict__ E,
                                                           const int* __restrict__ nodes, const int* __restrict__ map,
@@ -199,37 +117,54 @@ __global__ __launch_bounds__(256) void rows_by_map_kernel(float* __restrict__ D,
     reinterpret_cast<float4*>(D)[static_cast<int64_t>(r) * q + c] = reinterpret_cast<const float4*>(E)[t];
 }
 
-}  // namespace
+void ok(int rc) {
+    if (rc != GS_OK) fail(rc, gs_last_error());
+}
 
-// train_full_run restricted to the receptive field of `nodes` (full_field.hip).  The H_l tables stay N-row and
-// indexed by global id, so col and the gather loop are unchanged: layer l scatters its n_l output rows into H_l
-// and reads H_{l-1} on R_{l-1}, which layer l - 1 wrote.  A_l, argmax_l, dSelf and dA are compact in R_l order, and
-// so is dH_l (unlike H_l: the GEMMs read dZ_l as n_l consecutive rows, the workspace has no spare [n_l, H]
-// buffer to gather them into when L == 1, and the backward aggregate can write row pos_{l-1}[u] as cheaply as
-// row u).  The forward GEMM's compact output waits in dH's first buffer, which is free until the head.  No
-// launch here works on N x width: no memset of dH_L (the head's rows are R_L, each written in full), and the
-// restricted backward writes every row of R_{l-1}.
-void train_full_field_run(const FullPlan& p, const gs_full_plan_dev& d, const FullPlan& tp, const gs_full_plan_dev& td,
-                          const gs_train_full_config& c, const gs_full_field& f, const int32_t* nodes, int64_t B,
-                          int reuse_agg1, int stages, float* loss, void* ws, int64_t ws_bytes, hipStream_t st) {
+// The rows layer l computes: all N, or R_l of a field.
+struct LayerRows {
+    int64_t n = 0;                   // N, or n_l
+    const int* sidx = nullptr;       // the GEMMs' self rows: NULL (row i is node i), or R_l
+    const FieldLayer* fl = nullptr;  // what the aggregates take: NULL, or the field's layer
+};
+
+// The step over all N rows (f NULL), or restricted to the receptive field f of `nodes`.  Restricted, the H_l tables
+// stay N-row and indexed by global id, so col and the gather loop are unchanged: layer l scatters its n_l output
+// rows into H_l and reads H_{l-1} on R_{l-1}, which layer l - 1 wrote.  A_l, argmax_l, dSelf and dA are compact in
+// R_l order, and so is dH_l (unlike H_l: the GEMMs read dZ_l as n_l consecutive rows, the workspace has no spare
+// [n_l, H] buffer to gather them into when L == 1, and the backward aggregate can write row pos_{l-1}[u] as
+// cheaply as row u).  The forward GEMM's compact output waits in dH's first buffer, which is free until the head.
+// No restricted launch works on N x width: no memset of dH_L (the head's rows are R_L, each written in full), and
+// the restricted backward writes every row of R_{l-1}.  Every refusal names the path the caller took.
+void train_full_run(const FullPlan& p, const gs_full_plan_dev& d, const FullPlan& tp, const gs_full_plan_dev& td,
+                    const gs_train_full_config& c, const gs_full_field* f, const int32_t* nodes, int64_t B,
+                    int reuse_agg1, int stages, float* loss, void* ws, int64_t ws_bytes, hipStream_t st) {
     const TrainLayout lo = layout_of(p, tp, c);
     const int64_t H = c.hidden, L = c.n_layers, C = c.n_classes, m = p.gcn ? 1 : 2;
-    GS_REQUIRE(c.X && c.row_ptr && c.col && c.t_row_ptr && c.t_col && c.labels && c.params && c.grads && loss,
-               GS_EINVAL, "NULL pointer");
-    GS_REQUIRE(nodes && B >= 1 && B <= c.max_nodes, GS_EINVAL, "nodes: 1 to max_nodes ids");
-    GS_REQUIRE(stages >= 1 && stages <= GS_TF_ALL, GS_EINVAL, "bad stages");
-    GS_REQUIRE(ws && ws_bytes >= lo.total && (reinterpret_cast<uintptr_t>(ws) & (kAlign - 1)) == 0, GS_EINVAL,
-               "workspace smaller than gs_train_full_ws_bytes or not 256-byte aligned");
-    GS_REQUIRE(aligned16(c.params) && aligned16(c.grads), GS_EINVAL, "params / grads must be 16-byte aligned");
-    GS_REQUIRE(f.n_layers == L, GS_EINVAL, "the field was built for another number of layers");
+    auto require = [&](bool cond, const char* msg) {
+        if (!cond) fail(GS_EINVAL, std::string(f ? "train_full_field_run: " : "train_full_run: ") + msg);
+    };
+    require(c.X && c.row_ptr && c.col && c.t_row_ptr && c.t_col && c.labels && c.params && c.grads && loss,
+            "NULL pointer");
+    require(nodes && B >= 1 && B <= c.max_nodes, "nodes: 1 to max_nodes ids");
+    require(stages >= 1 && stages <= GS_TF_ALL, "bad stages");
+    require(ws && ws_bytes >= lo.total && (reinterpret_cast<uintptr_t>(ws) & (kAlign - 1)) == 0,
+            "workspace smaller than gs_train_full_ws_bytes or not 256-byte aligned");
+    require(aligned16(c.params) && aligned16(c.grads), "params / grads must be 16-byte aligned");
+    require(!f || f->n_layers == L, "the field was built for another number of layers");
     if (!p.empty_rows.empty())
         fail(GS_EEMPTY, "gs_train_full: a node's effective neighbourhood is empty (reference: models.py:313, :321-325)");
     FieldLayer fl[GS_MAX_HOPS + 1];
-    for (int l = 1; l <= L; ++l) fl[l] = field_layer(p, tp, f, l);
-    GS_REQUIRE(fl[L].n == B, GS_EINVAL, "the field was built for another set of nodes");
+    LayerRows rows[GS_MAX_HOPS + 1];
+    for (int l = 1; l <= L; ++l) {
+        if (f) fl[l] = field_layer(p, tp, *f, l);
+        rows[l] = f ? LayerRows{fl[l].n, fl[l].rows, &fl[l]} : LayerRows{p.n, nullptr, nullptr};
+    }
+    require(!f || fl[L].n == B, "the field was built for another set of nodes");
     char* base = static_cast<char*>(ws);
     const gs_agg op = static_cast<gs_agg>(c.agg);
     auto fptr = [&](int64_t o) { return reinterpret_cast<float*>(base + o); };
+    // the flat parameter layout: W_1 .. W_L, Wc, bc
     int64_t woff[GS_MAX_HOPS + 1];
     woff[0] = 0;
     for (int l = 1; l <= L; ++l) woff[l] = woff[l - 1] + H * m * in_width(c, l);
@@ -238,59 +173,75 @@ void train_full_field_run(const FullPlan& p, const gs_full_plan_dev& d, const Fu
 
     if (stages & GS_TF_FORWARD) {
         if (lo.w1lp >= 0) ok(gs_cast_f32_bf16(c.params, base + lo.w1lp, H * m * c.feat_dim, st));
-        float* tmp = fptr(lo.dh[0]);  // the GEMM's compact output rows, scattered into H_l
         for (int l = 1; l <= L; ++l) {
+            const LayerRows& r = rows[l];
             const gs_dtype dt = l == 1 ? static_cast<gs_dtype>(c.feat_dtype) : GS_F32;
             const char* in = l == 1 ? static_cast<const char*>(c.X) : base + lo.h[l - 2];
-            const int64_t ldin = l == 1 ? c.feat_ld : H, fin = in_width(c, l), nl = fl[l].n;
+            const int64_t ldin = l == 1 ? c.feat_ld : H, fin = in_width(c, l);
             if (lo.am[l - 1] >= 0)
                 agg_full_argmax_launch(p, d, dt, in, ldin, fin, c.row_ptr, c.col, 0, p.n, base + lo.a[l - 1], fin,
                                        reinterpret_cast<int32_t*>(base + lo.am[l - 1]), fin, base + lo.part,
-                                       lo.part_bytes, st, &fl[l]);
+                                       lo.part_bytes, st, r.fl);
             else if (l > 1 || !reuse_agg1)
                 agg_full_launch(p, d, op, dt, in, ldin, fin, c.row_ptr, c.col, 0, p.n, base + lo.a[l - 1], fin,
-                                base + lo.part, lo.part_bytes, st, &fl[l]);
+                                base + lo.part, lo.part_bytes, st, r.fl);
             const void* W = (l == 1 && lo.w1lp >= 0) ? static_cast<const void*>(base + lo.w1lp)
                                                      : static_cast<const void*>(c.params + woff[l - 1]);
-            linear_fwd_launch(dt, nl, fin, H, p.gcn ? nullptr : in, ldin, fl[l].rows, base + lo.a[l - 1], fin, W, tmp,
-                              H, 1, st);
-            rows_by_id_kernel<true><<<dim3(static_cast<unsigned>((nl * q + 255) / 256)), 256, 0, st>>>(
-                fptr(lo.h[l - 1]), tmp, fl[l].rows, nl, q);
-            check_launch("gs_train_full_field(scatter H)");
+            // straight into H_l, or the compact rows into dH's first buffer and from there to their rows of H_l
+            float* hl = fptr(lo.h[l - 1]);
+            float* out = f ? fptr(lo.dh[0]) : hl;
+            linear_fwd_launch(dt, r.n, fin, H, p.gcn ? nullptr : in, ldin, r.sidx, base + lo.a[l - 1], fin, W, out, H,
+                              1, st);
+            if (f) {
+                rows_by_id_kernel<true><<<dim3(static_cast<unsigned>((r.n * q + 255) / 256)), 256, 0, st>>>(
+                    hl, out, r.sidx, r.n, q);
+                check_launch("gs_train_full_field(scatter H)");
+            }
         }
     }
     float* dh_top = fptr(lo.dh[(L - 1) % 2]);
     if (stages & GS_TF_HEAD) {
         const unsigned grid = static_cast<unsigned>((B * q + 255) / 256);
         rows_by_id_kernel<false><<<dim3(grid), 256, 0, st>>>(fptr(lo.h[L - 1]), fptr(lo.e), nodes, B, q);
-        check_launch("gs_train_full_field(gather)");
+        check_launch(f ? "gs_train_full_field(gather)" : "gs_train_full(gather)");
+        // dE masked by relu'(H_L): the rows of dZ_L, every other row of it zero
         ok(gs_cls_nll_fwd_bwd(B, H, C, fptr(lo.e), c.params + wc_off, c.params + bc_off, c.labels, nodes, 1, loss,
                               fptr(lo.de), c.grads + wc_off, c.grads + bc_off, fptr(lo.cls), st));
-        // dZ_L, compact: R_L is `nodes`, so every one of its n_L rows is written
-        rows_by_map_kernel<<<dim3(grid), 256, 0, st>>>(dh_top, fptr(lo.de), nodes, fl[L].pos, B, q);
-        check_launch("gs_train_full_field(scatter dE)");
+        if (f) {  // dZ_L, compact: R_L is `nodes`, so every one of its n_L rows is written
+            rows_by_map_kernel<<<dim3(grid), 256, 0, st>>>(dh_top, fptr(lo.de), nodes, fl[L].pos, B, q);
+            check_launch("gs_train_full_field(scatter dE)");
+        } else {
+            GS_REQUIRE(hipMemsetAsync(dh_top, 0, p.n * H * 4, st) == hipSuccess, GS_EHIP, "memset failed");
+            rows_by_id_kernel<true><<<dim3(grid), 256, 0, st>>>(dh_top, fptr(lo.de), nodes, B, q);
+            check_launch("gs_train_full(scatter)");
+        }
     }
     if (stages & GS_TF_BACKWARD) {
         for (int l = static_cast<int>(L); l >= 1; --l) {
+            const LayerRows& r = rows[l];
             const gs_dtype dt = l == 1 ? static_cast<gs_dtype>(c.feat_dtype) : GS_F32;
             const char* in = l == 1 ? static_cast<const char*>(c.X) : base + lo.h[l - 2];
-            const int64_t ldin = l == 1 ? c.feat_ld : H, fin = in_width(c, l), nl = fl[l].n;
-            const float* dz = fptr(lo.dh[(l - 1) % 2]);  // dH_l on R_l, already masked by relu'(H_l)
+            const int64_t ldin = l == 1 ? c.feat_ld : H, fin = in_width(c, l);
+            const float* dz = fptr(lo.dh[(l - 1) % 2]);  // dH_l on the layer's rows, already masked by relu'(H_l)
             float* dW = c.grads + woff[l - 1];
-            const int S = linear_dw_slabs(dt, nl, fin, H, p.gcn ? nullptr : in, ldin, fl[l].rows, base + lo.a[l - 1],
-                                          fin, dz, nullptr, H, 0, dW, base + lo.slab, lo.slab_bytes, st, -1,
-                                          nl >= 512 ? kDw1Phases : 1);
+            // gs_sage_linear_bwd_weight's two launches: row slabs, then their sum in slab order
+            const int S = linear_dw_slabs(dt, r.n, fin, H, p.gcn ? nullptr : in, ldin, r.sidx, base + lo.a[l - 1], fin,
+                                          dz, nullptr, H, 0, dW, base + lo.slab, lo.slab_bytes, st, -1,
+                                          r.n >= 512 ? kDw1Phases : 1);
             if (S > 1) sum_slabs_launch(fptr(lo.slab), S, H * m * fin, dW, nullptr, st);
             if (l == 1) break;  // the feature table has no gradient
             float* dself = p.gcn ? nullptr : fptr(lo.dself);
-            ok(gs_sage_linear_bwd_input(nl, H, H, dz, nullptr, H, 0, c.params + woff[l - 1], dself, fptr(lo.da), H, st));
+            ok(gs_sage_linear_bwd_input(r.n, H, H, dz, nullptr, H, 0, c.params + woff[l - 1], dself, fptr(lo.da), H,
+                                        st));
             agg_full_bwd_launch(tp, td, op, H, c.t_row_ptr, c.t_col, fptr(lo.da), dself, H,
                                 lo.am[l - 1] >= 0 ? reinterpret_cast<const int32_t*>(base + lo.am[l - 1]) : nullptr, H,
                                 fptr(lo.h[l - 2]), fptr(lo.dh[(l - 2) % 2]), H, base + lo.part, lo.part_bytes, st,
-                                &fl[l], H);
+                                r.fl, H);
         }
     }
 }
+
+}  // namespace
 
 }  // namespace gs
 
@@ -303,34 +254,28 @@ int gs_train_full_field_forward_backward(const gs_full_plan* plan, const gs_full
                                          float* loss, void* ws, int64_t ws_bytes, void* stream) {
     GS_API_BEGIN
     GS_REQUIRE(plan && dev && tplan && tdev && cfg && f, GS_EINVAL, "NULL argument");
-    gs::train_full_field_run(*reinterpret_cast<const gs::FullPlan*>(plan), *dev,
-                             *reinterpret_cast<const gs::FullPlan*>(tplan), *tdev, *cfg, *f, nodes, n_nodes, reuse_agg1,
-                             stages, loss, ws, ws_bytes, gs::as_stream(stream));
+    gs::train_full_run(*reinterpret_cast<const gs::FullPlan*>(plan), *dev,
+                       *reinterpret_cast<const gs::FullPlan*>(tplan), *tdev, *cfg, f, nodes, n_nodes, reuse_agg1,
+                       stages, loss, ws, ws_bytes, gs::as_stream(stream));
     GS_API_END
 }
 
 int64_t gs_train_full_ws_bytes(const gs_full_plan* plan, const gs_full_plan* tplan, const gs_train_full_config* cfg) {
-    try {
-        if (!plan || !tplan || !cfg) return -1;
-        return gs::layout_of(*reinterpret_cast<const gs::FullPlan*>(plan),
-                             *reinterpret_cast<const gs::FullPlan*>(tplan), *cfg).total;
-    } catch (const std::exception& e) {
-        gs::set_error(e.what());
-        return -1;
-    }
+    GS_BYTES_BEGIN
+    if (!plan || !tplan || !cfg) return -1;
+    return gs::layout_of(*reinterpret_cast<const gs::FullPlan*>(plan),
+                         *reinterpret_cast<const gs::FullPlan*>(tplan), *cfg).total;
+    GS_BYTES_END
 }
 
 int64_t gs_train_full_ws_offset(const gs_full_plan* plan, const gs_full_plan* tplan, const gs_train_full_config* cfg,
                                 int32_t which, int32_t layer) {
-    try {
-        if (!plan || !tplan || !cfg || layer < 1 || layer > cfg->n_layers || which < 0 || which > 1) return -1;
-        const gs::TrainLayout lo = gs::layout_of(*reinterpret_cast<const gs::FullPlan*>(plan),
-                                                 *reinterpret_cast<const gs::FullPlan*>(tplan), *cfg);
-        return which == 0 ? lo.h[layer - 1] : lo.a[layer - 1];
-    } catch (const std::exception& e) {
-        gs::set_error(e.what());
-        return -1;
-    }
+    GS_BYTES_BEGIN
+    if (!plan || !tplan || !cfg || layer < 1 || layer > cfg->n_layers || which < 0 || which > 1) return -1;
+    const gs::TrainLayout lo = gs::layout_of(*reinterpret_cast<const gs::FullPlan*>(plan),
+                                             *reinterpret_cast<const gs::FullPlan*>(tplan), *cfg);
+    return which == 0 ? lo.h[layer - 1] : lo.a[layer - 1];
+    GS_BYTES_END
 }
 
 int gs_train_full_forward_backward(const gs_full_plan* plan, const gs_full_plan_dev* dev, const gs_full_plan* tplan,
@@ -340,8 +285,8 @@ int gs_train_full_forward_backward(const gs_full_plan* plan, const gs_full_plan_
     GS_API_BEGIN
     GS_REQUIRE(plan && dev && tplan && tdev && cfg, GS_EINVAL, "NULL argument");
     gs::train_full_run(*reinterpret_cast<const gs::FullPlan*>(plan), *dev,
-                       *reinterpret_cast<const gs::FullPlan*>(tplan), *tdev, *cfg, nodes, n_nodes, reuse_agg1, stages,
-                       loss, ws, ws_bytes, gs::as_stream(stream));
+                       *reinterpret_cast<const gs::FullPlan*>(tplan), *tdev, *cfg, nullptr, nodes, n_nodes, reuse_agg1,
+                       stages, loss, ws, ws_bytes, gs::as_stream(stream));
     GS_API_END
 }
 

@@ -302,40 +302,54 @@ def agg_full_bwd(agg_func, dA, graph, dH=None, *, gcn=False, seg_len=None, dSelf
             raise ValueError("agg_full_bwd: the field was built for another plan")
         if not field.build_id or layer is None or not 1 <= int(layer) <= field.n_layers:
             raise ValueError("agg_full_bwd: a built field and a layer in 1 .. field.n_layers expected")
-        return _agg_full_bwd_field(agg_func, dA, field, int(layer), dH, dSelf, argmax, Hprev, ws)
-    if layer is not None:
-        raise ValueError("agg_full_bwd: layer goes with a field")
-    if isinstance(graph, FullPlan):
-        tplan = graph if graph.is_transposed else graph.transposed()
+        layer = int(layer)
+        # rows of dA / dSelf / argmax, of Hprev and of dH, and their names in the messages
+        na, nh, nd, ra, rd = field.size(layer), tplan.n_nodes, field.size(layer - 1), "n_layer", "n_{layer-1}"
     else:
-        tplan = agg_full_bwd_plan(graph, gcn=gcn, seg_len=seg_len)
+        if layer is not None:
+            raise ValueError("agg_full_bwd: layer goes with a field")
+        if isinstance(graph, FullPlan):
+            tplan = graph if graph.is_transposed else graph.transposed()
+        else:
+            tplan = agg_full_bwd_plan(graph, gcn=gcn, seg_len=seg_len)
+        na = nh = nd = tplan.n_nodes
+        ra = rd = "n_nodes"
     op = agg_op(agg_func)
-    n = tplan.n_nodes
-    if dA.dtype != torch.float32 or dA.dim() != 2 or dA.stride(1) != 1 or dA.shape[0] != n:
-        raise ValueError("dA must be float32 [n_nodes, F] with unit column stride")
+
+    def ok(t, rows, width=0, dtype=torch.float32):
+        return t.dtype == dtype and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] == rows and t.shape[1] >= width
+
+    if not ok(dA, na):
+        raise ValueError(f"dA must be float32 [{ra}, F] with unit column stride")
     F = dA.shape[1]
     if dH is None:
-        dH = torch.empty(n, F, dtype=torch.float32, device=dA.device)
-    for name, t, like in (("dH", dH, None), ("dSelf", dSelf, dA), ("Hprev", Hprev, dH)):
-        if t is None:
-            continue
-        if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != n or t.shape[1] < F:
-            raise ValueError(f"{name} must be float32 [n_nodes, F] with unit column stride")
-        if like is not None and t.stride(0) != like.stride(0):
-            raise ValueError(f"{name} must share its leading dimension with {'dA' if like is dA else 'dH'}")
-    if op == _lib.GS_AGG_MAX:
-        if argmax is None or argmax.dtype != torch.int32 or argmax.dim() != 2 or argmax.stride(1) != 1 or \
-                argmax.shape[0] != n or argmax.shape[1] < F:
-            raise ValueError("MAX needs the forward's argmax: int32 [n_nodes, F]")
+        dH = torch.empty(nd, F, dtype=torch.float32, device=dA.device)
+    if not ok(dH, nd, F):
+        raise ValueError(f"dH must be float32 [{rd}, F] with unit column stride")
+    if dSelf is not None and (not ok(dSelf, na, F) or dSelf.stride(0) != dA.stride(0)):
+        raise ValueError(f"dSelf must be float32 [{ra}, F] and share dA's leading dimension")
+    # without a field Hprev and dH are both [n_nodes, F] and the native call takes one leading dimension for the two
+    if Hprev is not None and (not ok(Hprev, nh, F) or (field is None and Hprev.stride(0) != dH.stride(0))):
+        raise ValueError("Hprev must be float32 [n_nodes, F]" + (" and share dH's leading dimension" if field is None
+                                                                 else ""))
+    if op == _lib.GS_AGG_MAX and (argmax is None or not ok(argmax, na, F, torch.int32)):
+        raise ValueError(f"MAX needs the forward's argmax: int32 [{ra}, F]")
     need = int(lib().gs_agg_full_bwd_ws_bytes(tplan.handle, F))
     if need < 0:
         check(_lib.GS_EINVAL)
     if ws is None:
         ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dA.device)
     d, rp, cl = tplan.device(dA.device)
-    check(lib().gs_agg_full_bwd(tplan.handle, ctypes.byref(d), op, F, ptr(rp), ptr(cl), ptr(dA), ptr(dSelf),
-                                dA.stride(0), ptr(argmax), argmax.stride(0) if argmax is not None else 0, ptr(Hprev),
-                                ptr(dH), dH.stride(0), ptr(ws), ws.numel() * ws.element_size(), _stream(dA)))
+    lda = argmax.stride(0) if argmax is not None else 0
+    if field is None:
+        check(lib().gs_agg_full_bwd(tplan.handle, ctypes.byref(d), op, F, ptr(rp), ptr(cl), ptr(dA), ptr(dSelf),
+                                    dA.stride(0), ptr(argmax), lda, ptr(Hprev), ptr(dH), dH.stride(0), ptr(ws),
+                                    ws.numel() * ws.element_size(), _stream(dA)))
+    else:
+        check(lib().gs_agg_full_bwd_field(field.plan.handle, tplan.handle, ctypes.byref(d), field.ref, layer, op, F,
+                                          ptr(rp), ptr(cl), ptr(dA), ptr(dSelf), dA.stride(0), ptr(argmax), lda,
+                                          ptr(Hprev), Hprev.stride(0) if Hprev is not None else 0, ptr(dH),
+                                          dH.stride(0), ptr(ws), ws.numel() * ws.element_size(), _stream(dA)))
     return dH
 
 
@@ -535,41 +549,6 @@ def full_field(plan, tplan, nodes, n_layers, device=None, out=None):
     elif out.plan is not plan or out.tplan is not tplan or out.n_layers != int(n_layers):
         raise ValueError("full_field: `out` was made for other plans or another depth")
     return out.build(nodes)
-
-
-def _agg_full_bwd_field(agg_func, dA, field, layer, dH, dSelf, argmax, Hprev, ws):
-    import ctypes
-    tplan, op = field.tplan, agg_op(agg_func)
-    nl, nprev, n = field.size(layer), field.size(layer - 1), tplan.n_nodes
-
-    def ok(t, rows, dtype=torch.float32):
-        return t.dtype == dtype and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] == rows
-
-    if not ok(dA, nl):
-        raise ValueError("dA must be float32 [n_layer, F] with unit column stride")
-    F = dA.shape[1]
-    if dH is None:
-        dH = torch.empty(nprev, F, dtype=torch.float32, device=dA.device)
-    if not ok(dH, nprev) or dH.shape[1] < F:
-        raise ValueError("dH must be float32 [n_{layer-1}, F]")
-    if dSelf is not None and (not ok(dSelf, nl) or dSelf.shape[1] < F or dSelf.stride(0) != dA.stride(0)):
-        raise ValueError("dSelf must be float32 [n_layer, F] and share dA's leading dimension")
-    if Hprev is not None and (not ok(Hprev, n) or Hprev.shape[1] < F):
-        raise ValueError("Hprev must be float32 [n_nodes, F]")
-    if op == _lib.GS_AGG_MAX and (argmax is None or not ok(argmax, nl, torch.int32) or argmax.shape[1] < F):
-        raise ValueError("MAX needs the forward's argmax: int32 [n_layer, F]")
-    need = int(lib().gs_agg_full_bwd_ws_bytes(tplan.handle, F))
-    if need < 0:
-        check(_lib.GS_EINVAL)
-    if ws is None:
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dA.device)
-    d, rp, cl = tplan.device(dA.device)
-    check(lib().gs_agg_full_bwd_field(field.plan.handle, tplan.handle, ctypes.byref(d), field.ref, layer, op, F,
-                                      ptr(rp), ptr(cl), ptr(dA), ptr(dSelf), dA.stride(0), ptr(argmax),
-                                      argmax.stride(0) if argmax is not None else 0, ptr(Hprev),
-                                      Hprev.stride(0) if Hprev is not None else 0, ptr(dH), dH.stride(0), ptr(ws),
-                                      ws.numel() * ws.element_size(), _stream(dA)))
-    return dH
 
 
 def sage_linear_fwd(A, Wd, out, *, Xs=None, sidx=None, relu=True):

@@ -671,6 +671,7 @@ class FullEmbedder:
 
 # ------------------------------------------------------- full-batch training
 ReceptiveField = ops.ReceptiveField
+_FULL_AGG1 = "full"   # FullTrainer._agg1 after an unrestricted forward (no field's build_id)
 
 
 class FullTrainer:
@@ -780,8 +781,7 @@ class FullTrainer:
         self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
         self._ws_off = (-self._ws.data_ptr()) % 256
         self.cache_agg1 = bool(cache_agg1)
-        self._agg1_valid = False
-        self._agg1_field = 0   # build_id of the field whose compact A_1 the buffer holds (0: none)
+        self._agg1 = None      # whose A_1 the buffer holds: None, _FULL_AGG1 (all N rows), or a field's build_id
         self._opt_step = 0
         self.opt_m = self.opt_v = None
         if self._opt_kind == _lib.GS_OPT_ADAM:
@@ -820,8 +820,7 @@ class FullTrainer:
     def invalidate_cache(self):
         """Recompute layer 1's aggregate on the next step, full or restricted (the feature table changed in
         place)."""
-        self._agg1_valid = False
-        self._agg1_field = 0
+        self._agg1 = None
 
     def field(self, nodes, out=None):
         """The receptive field of `nodes` under this trainer's plans and depth
@@ -885,33 +884,28 @@ class FullTrainer:
         for measurement only.  `field`: field(nodes), to work on the batch's
         receptive field only (gs_train_full_field_forward_backward); hidden()
         then holds valid rows on R_l only."""
-        nodes = self._nodes(nodes)
-        if field is not None:
-            return self._field_forward_backward(nodes, stages, field)
-        reuse = self.cache_agg1 and self._agg1_valid
-        check(lib().gs_train_full_forward_backward(
-            self.plan.handle, ctypes.byref(self._dev), self.tplan.handle, ctypes.byref(self._tdev),
-            ctypes.byref(self.cfg), nodes.data_ptr(), nodes.numel(), int(reuse), int(stages), self.loss.data_ptr(),
-            self._ws.data_ptr() + self._ws_off, self.ws_bytes, _lib.stream_ptr(self.device)))
-        if stages & _lib.GS_TF_FORWARD:
-            self._agg1_valid = True
-            self._agg1_field = 0   # the buffer holds the N-row A_1 again
-        self._last_nodes = nodes  # alive until the stream has run the step
-        return self.loss
+        return self._forward_backward(self._nodes(nodes), stages, field)
 
-    def _field_forward_backward(self, nodes, stages, field):
-        self._check_field(field, nodes)
-        reuse = self.cache_agg1 and self._agg1_field == field.build_id
+    def _forward_backward(self, nodes, stages, field):
+        """Both paths' native call.  Layer 1's aggregate is reused only while the buffer holds this path's own
+        (all N rows, or this very build of the field); a forward stage makes the buffer this path's."""
+        head = (self.plan.handle, ctypes.byref(self._dev), self.tplan.handle, ctypes.byref(self._tdev),
+                ctypes.byref(self.cfg))
+        if field is None:
+            mine, fn = _FULL_AGG1, lib().gs_train_full_forward_backward
+        else:
+            self._check_field(field, nodes)
+            mine, fn, head = field.build_id, lib().gs_train_full_field_forward_backward, head + (field.ref,)
+        reuse = self.cache_agg1 and self._agg1 == mine
         if stages & _lib.GS_TF_FORWARD and not reuse:
-            self._agg1_valid = False  # the compact A_1 overwrites the full path's
-            self._agg1_field = 0
-        check(lib().gs_train_full_field_forward_backward(
-            self.plan.handle, ctypes.byref(self._dev), self.tplan.handle, ctypes.byref(self._tdev),
-            ctypes.byref(self.cfg), field.ref, nodes.data_ptr(), nodes.numel(), int(reuse), int(stages),
-            self.loss.data_ptr(), self._ws.data_ptr() + self._ws_off, self.ws_bytes, _lib.stream_ptr(self.device)))
+            self._agg1 = None  # this path's A_1 overwrites whatever the buffer held
+        check(fn(*head, nodes.data_ptr(), nodes.numel(), int(reuse), int(stages), self.loss.data_ptr(),
+                 self._ws.data_ptr() + self._ws_off, self.ws_bytes, _lib.stream_ptr(self.device)))
         if stages & _lib.GS_TF_FORWARD:
-            self._agg1_field = field.build_id
-        self._last_nodes, self._last_field = nodes, field  # alive until the stream has run the step
+            self._agg1 = mine
+        self._last_nodes = nodes  # alive until the stream has run the step
+        if field is not None:
+            self._last_field = field
         return self.loss
 
     def apply_update(self):
@@ -959,7 +953,7 @@ class FullTrainer:
             if nodes is None:
                 raise ValueError("FullTrainer.embed: a field goes with its nodes")
             nodes = self._nodes(nodes)
-            self._field_forward_backward(nodes, _lib.GS_TF_FORWARD, field)
+            self._forward_backward(nodes, _lib.GS_TF_FORWARD, field)
             return self.hidden().index_select(0, nodes.long())
         if self._embedder is None:
             self._embedder = FullEmbedder(self.graph, self.X, self.weights(), agg_func=self.agg, gcn=self.gcn,

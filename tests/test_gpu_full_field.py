@@ -352,7 +352,7 @@ def test_full_and_field_steps_interleaved(gs, case_id):
         want = fresh.forward_backward(nodes, **({"field": fresh.field(nodes)} if kind == "field" else {})).clone()
         torch.cuda.synchronize()
         assert torch.equal(loss, want) and torch.equal(tr.p.grads, fresh.p.grads), kind
-        assert tr._agg1_valid == (kind == "full") and (tr._agg1_field == field.build_id) == (kind == "field")
+        assert tr._agg1 == (train._FULL_AGG1 if kind == "full" else field.build_id)
         if kind == "field":
             L = case["L"]
             p0 = _np(tr.p.params)
@@ -363,7 +363,41 @@ def test_full_and_field_steps_interleaved(gs, case_id):
             _check_step(f"interleaved {case_id}", tr, field, loss, refs, case, ffc.factor("step", f"mix-{case_id}"))
         tr.apply_update()
     tr.invalidate_cache()
-    assert not tr._agg1_valid and tr._agg1_field == 0
+    assert tr._agg1 is None
+
+
+def test_cache_follows_full_and_two_fields(gs):
+    """full, A, A, B, full, invalidate_cache(), A on one trainer with
+    cache_agg1=True and two different fields A and B: after each call the loss
+    and the gradients are bitwise those of a trainer with cache_agg1=False
+    given the same calls -- the order in which a stale compact A_1 (the other
+    field's, or the N-row one) would be reused if the one cache variable named
+    the wrong owner."""
+    case = tc.STEP_BY_ID["l2"]
+    graph, n, rp, col, X, Xd, labels, params = _setup(case, "hub_max")
+    batch = {"A": ffc.FIELD_BY_ID["hub_four"]["nodes"], "B": np.array([0, 3, 200, 17, 125, 64])}
+    tr = _trainer(case, graph, Xd, labels, params, cache_agg1=True, lr=0.05)
+    plain = _trainer(case, graph, Xd, labels, params, cache_agg1=False, lr=0.05)
+    fields = {t: {k: t.field(v) for k, v in batch.items()} for t in (tr, plain)}
+    assert fields[tr]["A"].sizes != fields[tr]["B"].sizes and all(s < n for s in fields[tr]["B"].sizes[:-1])
+    owner = {"full": train._FULL_AGG1, "A": fields[tr]["A"].build_id, "B": fields[tr]["B"].build_id}
+    for call in ("full", "A", "A", "B", "full", "invalidate", "A"):
+        if call == "invalidate":
+            tr.invalidate_cache()
+            plain.invalidate_cache()
+            assert tr._agg1 is None
+            continue
+        got, want = [], []
+        for t, res in ((tr, got), (plain, want)):
+            if call == "full":
+                loss = t.forward_backward(batch["A"])
+            else:
+                loss = t.forward_backward(batch[call], field=fields[t][call])
+            res.extend((loss.clone(), t.p.grads.clone()))
+            t.apply_update()
+        assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]), call
+        assert float(got[1].abs().max()) > 0 and tr._agg1 == owner[call], call
+    assert torch.equal(tr.p.params, plain.p.params)
 
 
 @pytest.mark.parametrize("case_id", ["l2", "max_gcn"])

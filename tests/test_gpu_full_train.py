@@ -365,7 +365,7 @@ def test_cache_agg1_changes_no_bit(gs, case_id):
         assert torch.equal(a.p.grads, b.p.grads) and torch.equal(la, lb) and float(a.p.grads.abs().max()) > 0
         a.apply_update()
         b.apply_update()
-    assert torch.equal(a.p.params, b.p.params) and a._agg1_valid and torch.equal(a.hidden(1, 1), b.hidden(1, 1))
+    assert torch.equal(a.p.params, b.p.params) and a._agg1 == train._FULL_AGG1 and torch.equal(a.hidden(1, 1), b.hidden(1, 1))
     a.hidden(1, 1).zero_()                                 # a stale cache would now show
     a.invalidate_cache()
     a.forward_backward(nodes)
