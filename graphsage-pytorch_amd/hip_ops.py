@@ -651,6 +651,50 @@ def cls_nll_fwd_bwd(E, Wc, bc, labels, loss, dE, dWc, dbc, ws, roots=None, mask_
                                    ptr(dE), ptr(dWc), ptr(dbc), ptr(ws), _stream(E)))
 
 
+def unsup_loss_workspace(M, P, N, device):
+    """The buffer unsup_loss_fwd leaves for unsup_loss_bwd: {coef, cos, n1, n2} per pair (the P positive
+    pairs, then the N negative ones), then the M node scores at float offset 4 (P + N)."""
+    return torch.empty(int(lib().gs_unsup_loss_ws_floats(M, P, N)), dtype=torch.float32, device=device)
+
+
+def _unsup_args(E, plan, dims, ws):
+    M, P, N, U = (int(x) for x in dims)
+    if E.dtype != torch.float32 or E.dim() != 2 or E.stride(1) != 1 or E.shape[0] < U:
+        raise ValueError("embeddings must be float32 [U, D] with unit column stride")
+    if _i32(plan).dim() != 1 or not plan.is_contiguous() or plan.numel() < 2 * (M + 1) + 4 * (P + N) + U + 1:
+        raise ValueError("plan is shorter than its dims say")
+    if ws.dtype != torch.float32 or ws.dim() != 1 or not ws.is_contiguous() or ws.numel() < 4 * (P + N) + M:
+        raise ValueError("workspace must hold unsup_loss_workspace(M, P, N) floats")
+    return M, P, N, U
+
+
+def unsup_loss_fwd(kind, E, plan, dims, q, margin, ws):
+    """get_loss_sage (kind 0) / get_loss_margin (kind 1) over a device copy of gs_unsup_loss_plan
+    (gs_unsup_loss_fwd); dims = (M, P, N, U).  E is read as given, with its row stride; rows that are
+    not 16-byte aligned are refused (ValueError).  Fills ws, returns the loss (a 0-d tensor)."""
+    _dev(E, plan, ws)
+    M, P, N, U = _unsup_args(E, plan, dims, ws)
+    loss = torch.empty((), dtype=torch.float32, device=E.device)
+    check(lib().gs_unsup_loss_fwd(int(kind), M, P, N, U, E.shape[1], ptr(E), E.stride(0), ptr(plan), float(q),
+                                  float(margin), ptr(loss), ptr(ws), _stream(E)))
+    return loss
+
+
+def unsup_loss_bwd(E, plan, dims, ws, dloss, dE):
+    """dE = dloss * d loss / d E from the ws of unsup_loss_fwd on the same E and plan (gs_unsup_loss_bwd);
+    dloss: one float32 on the device.  Writes the rows [0, U) of dE over E's width, with dE's own stride."""
+    _dev(E, plan, ws, dloss, dE)
+    M, P, N, U = _unsup_args(E, plan, dims, ws)
+    if dE.dtype != torch.float32 or dE.dim() != 2 or dE.stride(1) != 1 or dE.shape[0] < U or \
+            dE.shape[1] != E.shape[1]:
+        raise ValueError("dE must be float32 [U, D] with unit column stride")
+    if dloss.dtype != torch.float32 or dloss.numel() != 1:
+        raise ValueError("dloss must be one float32")
+    check(lib().gs_unsup_loss_bwd(M, P, N, U, E.shape[1], ptr(E), E.stride(0), ptr(plan), ptr(ws), ptr(dloss),
+                                  ptr(dE), dE.stride(0), _stream(E)))
+    return dE
+
+
 def clip_sgd(goff, params, grads, grad_scale, max_norm, lr, ws):
     import numpy as np
     _dev(params, grads, ws)

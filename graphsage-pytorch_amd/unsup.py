@@ -19,7 +19,7 @@ import random as _pyrandom
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, hip_ops
 from ._lib import check, lib, ptr
 from .graph import CSRGraph
 from .sampler import RNG
@@ -311,11 +311,8 @@ class _UnsupLossFn(torch.autograd.Function):
             raise TypeError("embeddings must be float32")
         if E.stride(1) != 1 or E.stride(0) % 4 or E.data_ptr() % 16:
             E = E.contiguous()
-        D = E.shape[1]
-        ws = torch.empty(int(lib().gs_unsup_loss_ws_floats(M, P, N)), dtype=torch.float32, device=E.device)
-        loss = torch.empty((), dtype=torch.float32, device=E.device)
-        check(lib().gs_unsup_loss_fwd(kind, M, P, N, U, D, E.data_ptr(), E.stride(0), plan.data_ptr(), q, margin,
-                                      loss.data_ptr(), ws.data_ptr(), _lib.stream_ptr(E.device)))
+        ws = hip_ops.unsup_loss_workspace(M, P, N, E.device)
+        loss = hip_ops.unsup_loss_fwd(kind, E, plan, dims, q, margin, ws)
         ctx.save_for_backward(E, plan, ws)
         ctx.dims = dims
         return loss
@@ -323,10 +320,7 @@ class _UnsupLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss):
         E, plan, ws = ctx.saved_tensors
-        M, P, N, U = ctx.dims
         dl = dloss.detach().reshape(1).to(torch.float32).contiguous()
         dE = torch.empty_like(E)
-        check(lib().gs_unsup_loss_bwd(M, P, N, U, E.shape[1], E.data_ptr(), E.stride(0), plan.data_ptr(),
-                                      ws.data_ptr(), dl.data_ptr(), dE.data_ptr(), dE.stride(0),
-                                      _lib.stream_ptr(E.device)))
+        hip_ops.unsup_loss_bwd(E, plan, ctx.dims, ws, dl, dE)
         return dE, None, None, None, None, None
