@@ -210,6 +210,9 @@ _SIGS = {
                                      _i64, _vp, _i64, _vp, _i64, _vp]),
     "gs_train_full_field_forward_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp,
                                                     _i64, _vp]),
+    "gs_train_full_unsup_ws_bytes": (_i64, [_i32, _i64, _i64, _i64, _i64]),
+    "gs_train_full_unsup_forward_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32,
+                                                    _i32, _vp, _vp, _i64, _vp]),
 }
 
 (GS_FP_N_NODES, GS_FP_N_ITEMS, GS_FP_N_SLOTS, GS_FP_N_SPLIT, GS_FP_N_EMPTY, GS_FP_SEG_LEN, GS_FP_GCN,
@@ -244,6 +247,13 @@ class TrainFullConfig(ctypes.Structure):
         ("n_layers", _i32), ("hidden", _i32), ("n_classes", _i32), ("agg", _i32), ("feat_dtype", _i32),
         ("pad_", _i32), ("feat_dim", _i64), ("feat_ld", _i64), ("max_nodes", _i64), ("X", _vp), ("row_ptr", _vp),
         ("col", _vp), ("t_row_ptr", _vp), ("t_col", _vp), ("labels", _vp), ("params", _vp), ("grads", _vp),
+    ]
+
+
+class TrainFullUnsup(ctypes.Structure):
+    _fields_ = [
+        ("kind", _i32), ("with_sup", _i32), ("M", _i64), ("P", _i64), ("N", _i64), ("plan", _vp), ("q", _f32),
+        ("margin", _f32),
     ]
 
 

@@ -117,8 +117,58 @@ __global__ __launch_bounds__(256) void rows_by_map_kernel(float* __restrict__ D,
     reinterpret_cast<float4*>(D)[static_cast<int64_t>(r) * q + c] = reinterpret_cast<const float4*>(E)[t];
 }
 
+// The unsupervised head's last launch: dZ_L[target(i)] = E[i] > 0 ? dSup[i] + dNet[i] : 0 with target(i) =
+// nodes[i], or map[nodes[i]] (the field's pos_L, compact dH_L); dSup NULL: no supervised term.  Thread 0 also
+// folds the loss parts: loss[1] (the NLL mean, 0 without dSup) + loss[2] (the pair loss) -> loss[0].
+__global__ __launch_bounds__(256) void head_combine_kernel(float* __restrict__ D, const float* __restrict__ E,
+                                                           const float* __restrict__ dSup,
+                                                           const float* __restrict__ dNet,
+                                                           const int* __restrict__ nodes, const int* __restrict__ map,
+                                                           int64_t B, int q, float* __restrict__ loss) {
+    const int64_t t = blockIdx.x * int64_t(256) + threadIdx.x;
+    if (t == 0) {
+        const float sup = dSup ? loss[1] : 0.f;
+        loss[1] = sup;
+        loss[0] = dSup ? sup + loss[2] : loss[2];
+    }
+    if (t >= B * q) return;
+    const int64_t i = t / q;
+    const int c = static_cast<int>(t % q);
+    const int r = map ? map[nodes[i]] : nodes[i];
+    if (r < 0) return;  // not a root of this field: refused on the host before any launch
+    const float4 e = reinterpret_cast<const float4*>(E)[t];
+    float4 g = reinterpret_cast<const float4*>(dNet)[t];
+    if (dSup) {  // sup first, then net
+        const float4 s = reinterpret_cast<const float4*>(dSup)[t];
+        g = make_float4(s.x + g.x, s.y + g.y, s.z + g.z, s.w + g.w);
+    }
+    g = make_float4(e.x > 0.f ? g.x : 0.f, e.y > 0.f ? g.y : 0.f, e.z > 0.f ? g.z : 0.f, e.w > 0.f ? g.w : 0.f);
+    reinterpret_cast<float4*>(D)[static_cast<int64_t>(r) * q + c] = g;
+}
+
 void ok(int rc) {
     if (rc != GS_OK) fail(rc, gs_last_error());
+}
+
+// The caller's buffer of the unsupervised head: the loss kernels' per-pair state, dE of the pair loss and the
+// constant 1.0 that gs_unsup_loss_bwd reads as dloss.
+struct UnsupLayout {
+    int64_t pairs = 0, de = 0, one = 0, total = 0;
+};
+
+UnsupLayout unsup_layout_of(int64_t H, int64_t U, int64_t M, int64_t P, int64_t N) {
+    UnsupLayout lo;
+    lo.pairs = 0;
+    lo.de = round_up(gs_unsup_loss_ws_floats(M, P, N) * 4);
+    lo.one = lo.de + round_up(U * H * 4);
+    lo.total = lo.one + round_up(4);
+    return lo;
+}
+
+bool unsup_dims_ok(int64_t H, int64_t U, int64_t M, int64_t P, int64_t N) {
+    const int64_t cap = int64_t(1) << 30;
+    return H >= 16 && H <= 256 && H % 16 == 0 && U >= 1 && U < cap && M >= 1 && M < cap && P >= M && P < cap &&
+           N >= M && N < cap;
 }
 
 // The rows layer l computes: all N, or R_l of a field.
@@ -136,13 +186,19 @@ struct LayerRows {
 // cheaply as row u).  The forward GEMM's compact output waits in dH's first buffer, which is free until the head.
 // No restricted launch works on N x width: no memset of dH_L (the head's rows are R_L, each written in full), and
 // the restricted backward writes every row of R_{l-1}.  Every refusal names the path the caller took.
+//
+// u (nullable) swaps the head: the pair loss over E (unsup.hip) in place of, or with u->with_sup added to, the NLL
+// head, and head_combine_kernel in place of the scatter; `loss` then holds three floats.  The forward and the
+// backward stages do not know of it.
 void train_full_run(const FullPlan& p, const gs_full_plan_dev& d, const FullPlan& tp, const gs_full_plan_dev& td,
                     const gs_train_full_config& c, const gs_full_field* f, const int32_t* nodes, int64_t B,
-                    int reuse_agg1, int stages, float* loss, void* ws, int64_t ws_bytes, hipStream_t st) {
+                    const gs_train_full_unsup* u, void* uws, int64_t uws_bytes, int reuse_agg1, int stages,
+                    float* loss, void* ws, int64_t ws_bytes, hipStream_t st) {
     const TrainLayout lo = layout_of(p, tp, c);
     const int64_t H = c.hidden, L = c.n_layers, C = c.n_classes, m = p.gcn ? 1 : 2;
     auto require = [&](bool cond, const char* msg) {
-        if (!cond) fail(GS_EINVAL, std::string(f ? "train_full_field_run: " : "train_full_run: ") + msg);
+        const char* who = u ? "train_full_unsup_run: " : f ? "train_full_field_run: " : "train_full_run: ";
+        if (!cond) fail(GS_EINVAL, std::string(who) + msg);
     };
     require(c.X && c.row_ptr && c.col && c.t_row_ptr && c.t_col && c.labels && c.params && c.grads && loss,
             "NULL pointer");
@@ -161,6 +217,16 @@ void train_full_run(const FullPlan& p, const gs_full_plan_dev& d, const FullPlan
         rows[l] = f ? LayerRows{fl[l].n, fl[l].rows, &fl[l]} : LayerRows{p.n, nullptr, nullptr};
     }
     require(!f || fl[L].n == B, "the field was built for another set of nodes");
+    UnsupLayout ul;
+    if (u) {
+        require(u->kind == 0 || u->kind == 1, "kind: 0 = sage, 1 = margin");
+        require(u->M >= 1 && u->P >= 1 && u->N >= 1, "M, P and N must be at least 1");
+        require(unsup_dims_ok(H, B, u->M, u->P, u->N), "bad plan sizes (every scored node owns a pair of each sign)");
+        require(u->plan != nullptr, "NULL plan");
+        ul = unsup_layout_of(H, B, u->M, u->P, u->N);
+        require(uws && uws_bytes >= ul.total && (reinterpret_cast<uintptr_t>(uws) & (kAlign - 1)) == 0,
+                "unsup workspace smaller than gs_train_full_unsup_ws_bytes or not 256-byte aligned");
+    }
     char* base = static_cast<char*>(ws);
     const gs_agg op = static_cast<gs_agg>(c.agg);
     auto fptr = [&](int64_t o) { return reinterpret_cast<float*>(base + o); };
@@ -200,7 +266,29 @@ void train_full_run(const FullPlan& p, const gs_full_plan_dev& d, const FullPlan
         }
     }
     float* dh_top = fptr(lo.dh[(L - 1) % 2]);
-    if (stages & GS_TF_HEAD) {
+    if ((stages & GS_TF_HEAD) && u) {
+        const unsigned grid = static_cast<unsigned>((B * q + 255) / 256);
+        char* ub = static_cast<char*>(uws);
+        float* pairs = reinterpret_cast<float*>(ub + ul.pairs);
+        float* de_net = reinterpret_cast<float*>(ub + ul.de);
+        float* one = reinterpret_cast<float*>(ub + ul.one);
+        rows_by_id_kernel<false><<<dim3(grid), 256, 0, st>>>(fptr(lo.h[L - 1]), fptr(lo.e), nodes, B, q);
+        check_launch("gs_train_full_unsup(gather)");
+        GS_REQUIRE(hipMemsetD32Async(one, 0x3f800000, 1, st) == hipSuccess, GS_EHIP, "memset failed");  // 1.0f
+        ok(gs_unsup_loss_fwd(u->kind, u->M, u->P, u->N, B, H, fptr(lo.e), H, u->plan, u->q, u->margin, loss + 2,
+                             pairs, st));
+        ok(gs_unsup_loss_bwd(u->M, u->P, u->N, B, H, fptr(lo.e), H, u->plan, pairs, one, de_net, H, st));
+        if (u->with_sup)  // loss_sup over the whole extended batch, dE masked by relu'(H_L)
+            ok(gs_cls_nll_fwd_bwd(B, H, C, fptr(lo.e), c.params + wc_off, c.params + bc_off, c.labels, nodes, 1,
+                                  loss + 1, fptr(lo.de), c.grads + wc_off, c.grads + bc_off, fptr(lo.cls), st));
+        else  // the classifier takes no part in this loss
+            GS_REQUIRE(hipMemsetAsync(c.grads + wc_off, 0, (C * H + C) * 4, st) == hipSuccess, GS_EHIP,
+                       "memset failed");
+        if (!f) GS_REQUIRE(hipMemsetAsync(dh_top, 0, p.n * H * 4, st) == hipSuccess, GS_EHIP, "memset failed");
+        head_combine_kernel<<<dim3(grid), 256, 0, st>>>(dh_top, fptr(lo.e), u->with_sup ? fptr(lo.de) : nullptr,
+                                                        de_net, nodes, f ? fl[L].pos : nullptr, B, q, loss);
+        check_launch("gs_train_full_unsup(head combine)");
+    } else if (stages & GS_TF_HEAD) {
         const unsigned grid = static_cast<unsigned>((B * q + 255) / 256);
         rows_by_id_kernel<false><<<dim3(grid), 256, 0, st>>>(fptr(lo.h[L - 1]), fptr(lo.e), nodes, B, q);
         check_launch(f ? "gs_train_full_field(gather)" : "gs_train_full(gather)");
@@ -255,8 +343,8 @@ int gs_train_full_field_forward_backward(const gs_full_plan* plan, const gs_full
     GS_API_BEGIN
     GS_REQUIRE(plan && dev && tplan && tdev && cfg && f, GS_EINVAL, "NULL argument");
     gs::train_full_run(*reinterpret_cast<const gs::FullPlan*>(plan), *dev,
-                       *reinterpret_cast<const gs::FullPlan*>(tplan), *tdev, *cfg, f, nodes, n_nodes, reuse_agg1,
-                       stages, loss, ws, ws_bytes, gs::as_stream(stream));
+                       *reinterpret_cast<const gs::FullPlan*>(tplan), *tdev, *cfg, f, nodes, n_nodes, nullptr, nullptr,
+                       0, reuse_agg1, stages, loss, ws, ws_bytes, gs::as_stream(stream));
     GS_API_END
 }
 
@@ -271,10 +359,10 @@ int64_t gs_train_full_ws_bytes(const gs_full_plan* plan, const gs_full_plan* tpl
 int64_t gs_train_full_ws_offset(const gs_full_plan* plan, const gs_full_plan* tplan, const gs_train_full_config* cfg,
                                 int32_t which, int32_t layer) {
     GS_BYTES_BEGIN
-    if (!plan || !tplan || !cfg || layer < 1 || layer > cfg->n_layers || which < 0 || which > 1) return -1;
+    if (!plan || !tplan || !cfg || layer < 1 || layer > cfg->n_layers || which < 0 || which > 2) return -1;
     const gs::TrainLayout lo = gs::layout_of(*reinterpret_cast<const gs::FullPlan*>(plan),
                                              *reinterpret_cast<const gs::FullPlan*>(tplan), *cfg);
-    return which == 0 ? lo.h[layer - 1] : lo.a[layer - 1];
+    return which == 0 ? lo.h[layer - 1] : which == 1 ? lo.a[layer - 1] : lo.dh[(layer - 1) % 2];
     GS_BYTES_END
 }
 
@@ -285,8 +373,29 @@ int gs_train_full_forward_backward(const gs_full_plan* plan, const gs_full_plan_
     GS_API_BEGIN
     GS_REQUIRE(plan && dev && tplan && tdev && cfg, GS_EINVAL, "NULL argument");
     gs::train_full_run(*reinterpret_cast<const gs::FullPlan*>(plan), *dev,
-                       *reinterpret_cast<const gs::FullPlan*>(tplan), *tdev, *cfg, nullptr, nodes, n_nodes, reuse_agg1,
-                       stages, loss, ws, ws_bytes, gs::as_stream(stream));
+                       *reinterpret_cast<const gs::FullPlan*>(tplan), *tdev, *cfg, nullptr, nodes, n_nodes, nullptr,
+                       nullptr, 0, reuse_agg1, stages, loss, ws, ws_bytes, gs::as_stream(stream));
+    GS_API_END
+}
+
+int64_t gs_train_full_unsup_ws_bytes(int32_t hidden, int64_t n_nodes, int64_t M, int64_t P, int64_t N) {
+    GS_BYTES_BEGIN
+    if (!gs::unsup_dims_ok(hidden, n_nodes, M, P, N)) return -1;
+    return gs::unsup_layout_of(hidden, n_nodes, M, P, N).total;
+    GS_BYTES_END
+}
+
+int gs_train_full_unsup_forward_backward(const gs_full_plan* plan, const gs_full_plan_dev* dev,
+                                         const gs_full_plan* tplan, const gs_full_plan_dev* tdev,
+                                         const gs_train_full_config* cfg, const gs_full_field* f,
+                                         const int32_t* nodes, int64_t n_nodes, const gs_train_full_unsup* u,
+                                         void* uws, int64_t uws_bytes, int32_t reuse_agg1, int32_t stages,
+                                         float* loss, void* ws, int64_t ws_bytes, void* stream) {
+    GS_API_BEGIN
+    GS_REQUIRE(plan && dev && tplan && tdev && cfg && u, GS_EINVAL, "NULL argument");
+    gs::train_full_run(*reinterpret_cast<const gs::FullPlan*>(plan), *dev,
+                       *reinterpret_cast<const gs::FullPlan*>(tplan), *tdev, *cfg, f, nodes, n_nodes, u, uws,
+                       uws_bytes, reuse_agg1, stages, loss, ws, ws_bytes, gs::as_stream(stream));
     GS_API_END
 }
 

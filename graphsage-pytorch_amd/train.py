@@ -674,6 +674,34 @@ ReceptiveField = ops.ReceptiveField
 _FULL_AGG1 = "full"   # FullTrainer._agg1 after an unrestricted forward (no field's build_id)
 
 
+class UnsupBatch:
+    """One extended batch of the unsupervised losses on the exact path
+    (FullTrainer.unsup_batch): the device `nodes` (int32, the plan's row
+    order), the native descriptor `desc` (a _lib.TrainFullUnsup over `plan`)
+    and the head's buffer `uws` (uws_ptr: 256-byte aligned, uws_bytes)."""
+
+    def __init__(self, nodes, plan, dims, kind, learn_method, q, margin, uws, uws_bytes):
+        self.nodes, self.plan, self.dims = nodes, plan, dims
+        self.kind, self.learn_method, self.with_sup = kind, learn_method, learn_method == "plus_unsup"
+        M, P, N, _U = dims
+        self.desc = _lib.TrainFullUnsup(kind=0 if kind == "normal" else 1, with_sup=int(self.with_sup), M=M, P=P,
+                                        N=N, plan=plan.data_ptr(), q=q, margin=margin)
+        self.uws = uws
+        self.uws_off = (-uws.data_ptr()) % 256
+        self.uws_ptr, self.uws_bytes = uws.data_ptr() + self.uws_off, int(uws_bytes)
+
+    def pair_state(self):
+        """[P + N, 4] {coef, cos, n1, n2} per pair as the last head left them (positive pairs first)."""
+        _M, P, N, _U = self.dims
+        return self.uws[self.uws_off:self.uws_off + 16 * (P + N)].view(torch.float32).view(P + N, 4)
+
+    def d_embeddings(self, hidden):
+        """[U, hidden] dE of the pair loss as the last head left it."""
+        M, P, N, U = self.dims
+        off = self.uws_off + -(-4 * int(lib().gs_unsup_loss_ws_floats(M, P, N)) // 256) * 256
+        return self.uws[off:off + 4 * U * hidden].view(torch.float32).view(U, hidden)
+
+
 class FullTrainer:
     """Exact full-batch training over full neighbourhoods: the reference's
     num_sample=None branch (models.py:280-289) put through loss.backward(),
@@ -722,7 +750,25 @@ class FullTrainer:
     row outside the field has a gradient of exactly zero), at a cost that
     follows the field instead of N.  The workspace keeps its size.
 
-    Single GPU.  Out of scope: data parallel, and the unsupervised losses."""
+    The unsupervised losses (reference learn_method "unsup" and "plus_unsup",
+    utils.py:159-181): unsup_batch(source, kind, learn_method) describes one
+    extended batch -- an unsup.UnsupervisedLoss after extend_nodes, whose pair
+    plan and unique_nodes_batch it takes -- and forward_backward / step /
+    embed with `unsup=` then run the same forward and backward with another
+    head (gs_train_full_unsup_forward_backward): get_loss_sage ("normal") or
+    get_loss_margin ("margin") over H_L[nodes], plus the NLL mean over the
+    same rows under "plus_unsup".  loss_parts() holds (total, loss_sup,
+    loss_net).  Under "unsup" the classifier has no gradient in the reference
+    and its optimisers skip it: apply_update after such a step updates the
+    sage group only and leaves the classifier's parameters and Adam moments
+    bitwise unchanged (no weight decay either).  The trainer keeps ONE step
+    counter, which still advances, so the classifier's next Adam update is
+    bias-corrected with the trainer's step, not with a count of its own
+    updates as torch.optim would.  unsup_step(unsupervised_loss, batch_ids,
+    ...) is one apply_model batch: extend, plan, field, step; nothing on this
+    path draws from a `random` stream but extend_nodes itself.
+
+    Single GPU.  Out of scope: data parallel."""
 
     def __init__(self, graph, features, labels, n_classes, num_layers=2, hidden=128, agg_func="MEAN", gcn=False,
                  lr=0.7, max_norm=5.0, seed=824, weights=None, optimizer="sgd", betas=(0.9, 0.999), eps=1e-8,
@@ -765,7 +811,11 @@ class FullTrainer:
         self.tplan = self.plan.transposed(ops.FULL_BWD_SEG_LEN if seg_len is None else seg_len)
         self._dev, self.row_ptr, self.col = self.plan.device(self.device)
         self._tdev, self.t_row_ptr, self.t_col = self.tplan.device(self.device)
-        self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._loss3 = torch.zeros(3, dtype=torch.float32, device=self.device)  # total, loss_sup, loss_net
+        self.loss = self._loss3[:1]
+        self._uws = None           # the unsupervised head's buffer: grows on demand, kept between batches
+        self._cls_frozen = False   # the last head was 'unsup': the classifier takes no update
+        self._unsup_field = None   # unsup_step's field, rebuilt in place
         self.clip_ws = torch.empty(65 * 2, dtype=torch.float32, device=self.device)
         self.cfg = _lib.TrainFullConfig(
             n_layers=self.L, hidden=self.H, n_classes=self.C, agg=op,
@@ -874,20 +924,84 @@ class FullTrainer:
             raise IndexError("FullTrainer: node id out of range")
         if len(np.unique(a)) != a.size:
             raise ValueError("FullTrainer: duplicate ids in nodes")
-        return torch.from_numpy(a.astype(np.int32)).to(self.device)
+        t = torch.from_numpy(a.astype(np.int32)).to(self.device)
+        self._nodes_ok = (t.data_ptr(), t.numel(), t._version)  # checked above, on the host
+        return t
 
-    def forward_backward(self, nodes, stages=_lib.GS_TF_ALL, field=None):
+    def unsup_batch(self, source, kind="normal", learn_method="unsup", q=None, margin=None):
+        """One extended batch of the unsupervised losses, for `unsup=`.
+
+        `source`: an unsup.UnsupervisedLoss after extend_nodes / extend_nodes_array
+        (its pair plan and unique_nodes_batch are taken; q and margin default to
+        its Q and MARGIN), or a raw (plan int32 device tensor, (M, P, N, U), nodes)
+        triple laid out as gs_unsup_loss_plan, rows = positions in `nodes` (q and
+        margin then default to the reference's 10 and 3).  kind: "normal"
+        (get_loss_sage) or "margin" (get_loss_margin); learn_method: "unsup" or
+        "plus_unsup".  No scored node (M == 0) raises the ValueError the
+        reference's torch.cat raises."""
+        if kind not in ("normal", "margin"):
+            raise ValueError("FullTrainer.unsup_batch: kind must be 'normal' or 'margin'")
+        if learn_method not in ("unsup", "plus_unsup"):
+            raise ValueError("FullTrainer.unsup_batch: learn_method must be 'unsup' or 'plus_unsup'")
+        if isinstance(source, (tuple, list)):
+            plan, dims, nodes = source
+            dq, dm = 10.0, 3.0
+        else:
+            nodes = source._unique_array()
+            plan, dims = source._device_plan(self.device)
+            dq, dm = float(source.Q), float(source.MARGIN)
+        M, P, N, U = (int(x) for x in tuple(dims)[:4])
+        if M == 0:
+            raise ValueError("torch.cat(): expected a non-empty list of Tensors")
+        nodes = self._nodes(nodes)
+        if nodes.numel() != U:
+            raise ValueError(f"FullTrainer.unsup_batch: the plan has {U} rows, nodes holds {nodes.numel()} ids")
+        if M < 1 or P < M or N < M:
+            raise ValueError("FullTrainer.unsup_batch: every scored node owns a positive and a negative pair")
+        if not isinstance(plan, torch.Tensor) or plan.device != self.device or plan.dtype != torch.int32 or \
+                plan.dim() != 1 or not plan.is_contiguous() or plan.numel() < 2 * (M + 1) + 4 * (P + N) + U + 1:
+            raise ValueError("FullTrainer.unsup_batch: plan must be a contiguous int32 tensor on the trainer's "
+                             "device, as long as its dims say")
+        need = int(lib().gs_train_full_unsup_ws_bytes(self.H, U, M, P, N))
+        if need < 0:
+            raise ValueError("FullTrainer.unsup_batch: bad plan sizes")
+        if self._uws is None or self._uws.numel() < need + 256:
+            self._uws = torch.empty(need + need // 4 + 256, dtype=torch.uint8, device=self.device)
+        return UnsupBatch(nodes, plan, (M, P, N, U), kind, learn_method, dq if q is None else float(q),
+                          dm if margin is None else float(margin), self._uws, need)
+
+    def loss_parts(self):
+        """(total, loss_sup, loss_net) of the last step with `unsup=`, as device scalars (loss_sup is 0 under
+        "unsup")."""
+        return self._loss3[0], self._loss3[1], self._loss3[2]
+
+    def _check_unsup(self, unsup, nodes):
+        """`nodes` of a call with `unsup=`: the batch's own, checked before any launch."""
+        if not isinstance(unsup, UnsupBatch):
+            raise TypeError("FullTrainer: unsup must come from FullTrainer.unsup_batch")
+        if nodes is unsup.nodes:
+            return nodes
+        nodes = self._nodes(nodes)
+        if nodes.numel() != unsup.nodes.numel() or not torch.equal(nodes, unsup.nodes):
+            raise ValueError("FullTrainer: with unsup=, nodes must be the batch's own nodes (unsup.nodes)")
+        return unsup.nodes
+
+    def forward_backward(self, nodes, stages=_lib.GS_TF_ALL, field=None, unsup=None):
         """Loss (device scalar, the NLL mean over `nodes`) and the raw,
         unclipped gradients into self.p.grads: one native call that issues
         every launch of the step on the current stream.  `nodes`: unique ids,
         a device int32 vector or a host array.  `stages`: a _lib.GS_TF_* subset,
         for measurement only.  `field`: field(nodes), to work on the batch's
         receptive field only (gs_train_full_field_forward_backward); hidden()
-        then holds valid rows on R_l only."""
+        then holds valid rows on R_l only.  `unsup`: unsup_batch(...), whose
+        loss replaces (or, "plus_unsup", joins) the NLL mean; `nodes` must then
+        be unsup.nodes, the loss is the total and loss_parts() its terms."""
+        if unsup is not None:
+            return self._forward_backward(self._check_unsup(unsup, nodes), stages, field, unsup)
         return self._forward_backward(self._nodes(nodes), stages, field)
 
-    def _forward_backward(self, nodes, stages, field):
-        """Both paths' native call.  Layer 1's aggregate is reused only while the buffer holds this path's own
+    def _forward_backward(self, nodes, stages, field, unsup=None):
+        """Every path's native call.  Layer 1's aggregate is reused only while the buffer holds this path's own
         (all N rows, or this very build of the field); a forward stage makes the buffer this path's."""
         head = (self.plan.handle, ctypes.byref(self._dev), self.tplan.handle, ctypes.byref(self._tdev),
                 ctypes.byref(self.cfg))
@@ -896,37 +1010,74 @@ class FullTrainer:
         else:
             self._check_field(field, nodes)
             mine, fn, head = field.build_id, lib().gs_train_full_field_forward_backward, head + (field.ref,)
+        tail = ()
+        if unsup is not None:
+            fn = lib().gs_train_full_unsup_forward_backward
+            if field is None:
+                head = head + (None,)
+            tail = (ctypes.byref(unsup.desc), unsup.uws_ptr, unsup.uws_bytes)
         reuse = self.cache_agg1 and self._agg1 == mine
         if stages & _lib.GS_TF_FORWARD and not reuse:
             self._agg1 = None  # this path's A_1 overwrites whatever the buffer held
-        check(fn(*head, nodes.data_ptr(), nodes.numel(), int(reuse), int(stages), self.loss.data_ptr(),
+        check(fn(*head, nodes.data_ptr(), nodes.numel(), *tail, int(reuse), int(stages), self._loss3.data_ptr(),
                  self._ws.data_ptr() + self._ws_off, self.ws_bytes, _lib.stream_ptr(self.device)))
         if stages & _lib.GS_TF_FORWARD:
             self._agg1 = mine
+        if stages & _lib.GS_TF_HEAD:
+            self._cls_frozen = unsup is not None and not unsup.with_sup
         self._last_nodes = nodes  # alive until the stream has run the step
+        self._last_unsup = unsup
         if field is not None:
             self._last_field = field
         return self.loss
 
     def apply_update(self):
-        """clip per model + SGD, or + AdamW (gs_clip_sgd / gs_clip_adam) on the flat buffers."""
+        """clip per model + SGD, or + AdamW (gs_clip_sgd / gs_clip_adam) on the flat buffers.  After an 'unsup'
+        head the classifier's group is left out of the call: its parameters and moments are not touched."""
         self._opt_step += 1
+        goff = self.p.group_off[:2] if self._cls_frozen else self.p.group_off
         if self._opt_kind == _lib.GS_OPT_ADAM:
-            ops.clip_adam(self.p.group_off, self.p.params, self.p.grads, self.opt_m, self.opt_v, 1.0, self.max_norm,
+            ops.clip_adam(goff, self.p.params, self.p.grads, self.opt_m, self.opt_v, 1.0, self.max_norm,
                           self.lr, self.betas, self.eps, self.weight_decay, self._opt_step, self.clip_ws)
         else:
-            ops.clip_sgd(self.p.group_off, self.p.params, self.p.grads, 1.0, self.max_norm, self.lr, self.clip_ws)
+            ops.clip_sgd(goff, self.p.params, self.p.grads, 1.0, self.max_norm, self.lr, self.clip_ws)
 
-    def step(self, nodes, field=None):
-        loss = self.forward_backward(nodes, field=field)
+    def step(self, nodes, field=None, unsup=None):
+        loss = self.forward_backward(nodes, field=field, unsup=unsup)
         self.apply_update()
         return loss
+
+    def unsup_step(self, unsupervised_loss, batch_ids, unsup_loss="normal", learn_method="unsup", num_neg=None,
+                   use_field=True):
+        """One apply_model batch (utils.py:113-193) on the exact path:
+        extend_nodes(batch_ids, num_neg) on `unsupervised_loss`, its pair plan,
+        the receptive field of the extended batch (use_field) and one step.
+        num_neg: None takes the reference's 100 ("normal") or 6 ("margin").
+        Returns (loss, extended nodes as an int64 array); the only host
+        synchronisation is the field's."""
+        defaults = {"normal": 100, "margin": 6}
+        if unsup_loss not in defaults:
+            raise ValueError("FullTrainer.unsup_step: unsup_loss must be 'normal' or 'margin'")
+        if learn_method not in ("unsup", "plus_unsup"):
+            raise ValueError("FullTrainer.unsup_step: learn_method must be 'unsup' or 'plus_unsup'")
+        nodes = unsupervised_loss.extend_nodes_array(batch_ids, num_neg=defaults[unsup_loss] if num_neg is None
+                                                     else int(num_neg))
+        batch = self.unsup_batch(unsupervised_loss, kind=unsup_loss, learn_method=learn_method)
+        field = None
+        if use_field:
+            field = self._unsup_field = self.field(batch.nodes, out=self._unsup_field)
+        return self.step(batch.nodes, field=field, unsup=batch), nodes
 
     def hidden(self, layer=None, which=0):
         """A view of H_layer (which=0) or A_layer (which=1) as the last
         forward left it in the workspace ([N, width]; layer None: the last).
         After a field step H_layer holds valid rows on R_layer only, and
-        A_layer's first n_layer rows are the compact aggregate in R_layer order."""
+        A_layer's first n_layer rows are the compact aggregate in R_layer order.
+        which=2: the buffer of dH_layer (dZ_layer, masked by relu'), valid
+        until the backward of layer - 1 reuses it for dH_{layer-2} (two
+        buffers ping-pong): dZ_L is there after the head stage, and still
+        after the whole step when L <= 2; row v is node v, or after a field
+        step row i is R_layer[i] and only the first n_layer rows are written."""
         layer = self.L if layer is None else int(layer)
         off = int(lib().gs_train_full_ws_offset(self.plan.handle, self.tplan.handle, ctypes.byref(self.cfg), which,
                                                 layer))
@@ -941,19 +1092,21 @@ class FullTrainer:
         raw = self._ws[self._ws_off + off:self._ws_off + off + nbytes]
         return raw.view(dt).view(n, w)
 
-    def embed(self, nodes=None, field=None):
+    def embed(self, nodes=None, field=None, unsup=None):
         """[N, hidden] exact embeddings under the current weights (or the rows
         `nodes`): FullEmbedder over this trainer's parameter views, bitwise
         FullEmbedder(graph, X, tr.weights(), ...).embed().  `field`:
         field(nodes) -- the field path's forward stage alone, then the rows
         `nodes` of H_L (in the order of `nodes`); it overwrites the step's
         activations in the workspace.  Restricted inference without a trainer
-        is out of scope: FullEmbedder always computes all N rows."""
-        if field is not None:
+        is out of scope: FullEmbedder always computes all N rows.  `unsup`:
+        unsup_batch(...) -- the forward stage of the unsupervised step's own
+        entry point, then the rows of its nodes."""
+        if field is not None or unsup is not None:
             if nodes is None:
-                raise ValueError("FullTrainer.embed: a field goes with its nodes")
-            nodes = self._nodes(nodes)
-            self._forward_backward(nodes, _lib.GS_TF_FORWARD, field)
+                raise ValueError("FullTrainer.embed: a field or an unsup batch goes with its nodes")
+            nodes = self._check_unsup(unsup, nodes) if unsup is not None else self._nodes(nodes)
+            self._forward_backward(nodes, _lib.GS_TF_FORWARD, field, unsup)
             return self.hidden().index_select(0, nodes.long())
         if self._embedder is None:
             self._embedder = FullEmbedder(self.graph, self.X, self.weights(), agg_func=self.agg, gcn=self.gcn,

@@ -126,6 +126,43 @@ def apply_model(dataCenter, ds, graphSage, classification, unsupervised_loss, b_
     return graphSage, classification
 
 
+def apply_model_full(dataCenter, ds, trainer, unsupervised_loss, b_sz, unsup_loss, learn_method, verbose=True):
+    """apply_model's epoch on the exact path: the same shuffle, batches,
+    extend_nodes and print line, each batch one step of `trainer` (a
+    train.FullTrainer, which holds both models' parameters, its own clip and
+    optimiser) over the full neighbourhoods of the extended batch, restricted
+    to its receptive field.  "unsup" / "plus_unsup": FullTrainer.unsup_step;
+    "sup": extend_nodes, then the supervised step over the extended batch
+    (utils.py:153-164).  Nothing but the shuffle and extend_nodes draws from a
+    random stream.  Returns the trainer."""
+    if unsup_loss not in _NUM_NEG:
+        print("unsup_loss can be only 'margin' or 'normal'.")
+        sys.exit(1)
+    num_neg = _NUM_NEG[unsup_loss]
+    train_nodes = getattr(dataCenter, ds + "_train")
+    from sklearn.utils import shuffle  # numpy's global stream, as the reference
+    train_nodes = shuffle(train_nodes)
+
+    n_batches = math.ceil(len(train_nodes) / b_sz)
+    seen = set()
+    field = None
+    for index in range(n_batches):
+        batch = train_nodes[index * b_sz:(index + 1) * b_sz]
+        if learn_method == "sup":
+            nodes = unsupervised_loss.extend_nodes_array(batch, num_neg=num_neg)
+            ids = trainer._nodes(nodes)
+            field = trainer.field(ids, out=field)
+            loss = trainer.step(ids, field=field)
+        else:
+            loss, nodes = trainer.unsup_step(unsupervised_loss, batch, unsup_loss=unsup_loss,
+                                             learn_method=learn_method, num_neg=num_neg)
+        seen.update(nodes.tolist())
+        if verbose:
+            print(f"Step [{index + 1}/{n_batches}], Loss: {loss.item():.4f}, "
+                  f"Dealed Nodes [{len(seen)}/{len(train_nodes)}] ")
+    return trainer
+
+
 def _world(group):
     if dist.is_available() and dist.is_initialized():
         return dist.get_rank(group), dist.get_world_size(group)

@@ -965,7 +965,8 @@ typedef struct {
     float* grads;
 } gs_train_full_config;
 enum { GS_TF_FORWARD = 1, GS_TF_HEAD = 2, GS_TF_BACKWARD = 4, GS_TF_ALL = 7 };
-/* Byte offsets into ws of the kept activations (which: 0 = H_l, 1 = A_l; l = 1..L); -1 on error. */
+/* Byte offsets into ws of the kept activations (which: 0 = H_l, 1 = A_l, 2 = dH_l, the ping-pong buffer
+ * that holds dZ_l while layer l's backward reads it; l = 1..L); -1 on error. */
 int64_t gs_train_full_ws_offset(const gs_full_plan* plan, const gs_full_plan* tplan,
                                 const gs_train_full_config* cfg, int32_t which, int32_t layer);
 int64_t gs_train_full_ws_bytes(const gs_full_plan* plan, const gs_full_plan* tplan,
@@ -1058,6 +1059,41 @@ int gs_train_full_field_forward_backward(const gs_full_plan* plan, const gs_full
                                          const gs_full_plan* tplan, const gs_full_plan_dev* tdev,
                                          const gs_train_full_config* cfg, const gs_full_field* f,
                                          const int32_t* nodes, int64_t n_nodes,
+                                         int32_t reuse_agg1, int32_t stages, float* loss,
+                                         void* ws, int64_t ws_bytes, void* stream);
+
+/* The exact step under the unsupervised losses (reference learn_method 'unsup'
+ * and 'plus_unsup', utils.py:159-181): the forward and backward stages of the
+ * two calls above with another head.  nodes: the extended batch
+ * (unique_nodes_batch), n_nodes = U unique ids in the plan's row order; f: NULL
+ * for all N rows, or the field of `nodes`.  Head:
+ *   E = H_L[nodes]; loss_net = gs_unsup_loss_fwd(E), dE_net = gs_unsup_loss_bwd
+ *   (lde = hidden, dloss = 1); with_sup: loss_sup and the classifier's gradients
+ *   from gs_cls_nll_fwd_bwd over the same U rows, otherwise the classifier's
+ *   range of grads is set to zero; then one launch writes
+ *   dZ_L[target(i)] = E[i] > 0 ? dE_sup[i] + dE_net[i] : 0
+ *   (target(i) = nodes[i] in a zeroed dH_L, or POS_L[nodes[i]] in the compact one)
+ *   and loss[0..2] = {loss_sup + loss_net, loss_sup (0 without), loss_net}.
+ * uws: gs_train_full_unsup_ws_bytes bytes owned by the caller, 256-byte aligned:
+ * the loss kernels' per-pair state (gs_unsup_loss_ws_floats floats, at offset 0),
+ * dE_net [U, hidden] (at the next multiple of 256 bytes) and the constant 1.0.
+ * Nothing is allocated; the plan's contents are trusted as gs_unsup_loss_fwd
+ * trusts them.  GS_EINVAL before any launch: kind outside {0, 1}; M, P or N < 1
+ * (or P or N < M); uws too small or misaligned; a field built for other nodes or
+ * another depth; n_nodes > max_nodes. */
+typedef struct {
+    int32_t kind;        /* 0 = get_loss_sage, 1 = get_loss_margin */
+    int32_t with_sup;    /* 0: loss = loss_net ('unsup'); 1: loss = loss_sup + loss_net ('plus_unsup') */
+    int64_t M, P, N;     /* gs_unsup_loss_plan's dims; U is n_nodes */
+    const int32_t* plan; /* device copy of gs_unsup_loss_plan, rows = positions in `nodes` */
+    float q, margin;     /* reference: 10, 3 */
+} gs_train_full_unsup;
+int64_t gs_train_full_unsup_ws_bytes(int32_t hidden, int64_t n_nodes, int64_t M, int64_t P, int64_t N);
+int gs_train_full_unsup_forward_backward(const gs_full_plan* plan, const gs_full_plan_dev* dev,
+                                         const gs_full_plan* tplan, const gs_full_plan_dev* tdev,
+                                         const gs_train_full_config* cfg, const gs_full_field* f,
+                                         const int32_t* nodes, int64_t n_nodes,
+                                         const gs_train_full_unsup* u, void* uws, int64_t uws_bytes,
                                          int32_t reuse_agg1, int32_t stages, float* loss,
                                          void* ws, int64_t ws_bytes, void* stream);
 
