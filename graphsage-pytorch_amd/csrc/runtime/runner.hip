@@ -4,17 +4,27 @@
 // so that no Python code runs per step.
 //
 //   sampler thread w : batches w, w+S, ... in order, each into a free pinned
-//                      slot of its ring (gs_sample_pack_run, its own rng)
-//   gs_runner_run    : batch i from stream i % S, in order: device pull of
-//                      its pack (ring entry i % 3) and its layer-1 gather on
-//                      a side stream, issued one batch ahead when sampled so
-//                      they run under step i-1; then forward/backward from
-//                      the gathered slot, all-reduce (with a communicator) and update
-//                      on the caller's stream.
-// A pinned slot returns to its sampler once the copy that read it has
-// completed.  Only the driver thread makes HIP calls: it polls the copy events
-// of consumed slots (hipEventQuery) and hands finished slots back, and waits
-// on the oldest copy only when a stream has no slot left to sample into.
+//                      slot of its ring (gs_sample_pack_run, its own rng),
+//                      then the pack into the slot's device twin:
+//                      hipMemcpyAsync on the runner's copy stream and a
+//                      host wait for it, before the slot is offered
+//   gs_runner_run    : batch i from stream i % S, in order: its layer-1
+//                      gather from the slot's device twin on a side stream,
+//                      issued one batch ahead when sampled so it runs under
+//                      step i-1; then forward/backward from the gathered
+//                      slot, all-reduce (with a communicator) and update on
+//                      the caller's stream.
+// The pack moves when it is final, many steps before it is read, from the
+// thread that has the time for the copy call and its wait, and by the copy
+// engine: no wave on a CU reads host memory while a step runs.  The copy
+// stream carries copies only and the sampler thread waits on the host, so the
+// runtime queues no packet for it on the GPU: an event recorded behind each
+// copy (a barrier packet that waits for the copy engine in a hardware queue
+// beside the step's) cost the step ~3 us.
+// A slot (pinned buffer + device twin) returns to its sampler once the step
+// that read the twin has completed: the driver thread checks the step's done
+// flag / event as it goes, and waits for the oldest step only when a stream
+// has no slot left to sample into.
 #include <rccl/rccl.h>
 #include <sys/mman.h>
 
@@ -48,8 +58,8 @@ static void hip_ok(hipError_t e, const char* what) {
 }
 
 // The runner's events only order work: the host never reads device memory
-// through them (it waits on them before reusing a pinned slot the device has
-// read, or a device buffer whose readers have finished), and cross-stream
+// through them (it waits on them before reusing a slot whose device twin a
+// step has read, or a device buffer whose readers have finished), and cross-stream
 // consumers are ordered by them on one device.  So they skip the system-scope
 // release that a default event performs (a cache writeback + invalidate at
 // every step boundary).
@@ -57,32 +67,10 @@ static unsigned sync_event_flags() {
     return hipEventDisableTiming | static_cast<unsigned>(hipEventDisableSystemFence);
 }
 
-// Device-side pull of a pinned host pack (hipHostMalloc memory is mapped into
-// the device address space): the host pays one kernel launch instead of
-// hipMemcpyAsync's host-side cost (measured ~50 us per 0.3 MB pack).
-__global__ __launch_bounds__(256) void pull_pack_kernel(const int4* __restrict__ src, int4* __restrict__ dst,
-                                                        int64_t n16, const int32_t* __restrict__ src_tail,
-                                                        int32_t* __restrict__ dst_tail, int n_tail) {
-    // grid-stride, four 16-B loads in flight per lane before their stores
-    const int64_t stride = gridDim.x * int64_t(256);
-    for (int64_t i = blockIdx.x * int64_t(256) + threadIdx.x; i < n16; i += 4 * stride) {
-        int4 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            if (i + u * stride < n16) v[u] = src[i + u * stride];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            if (i + u * stride < n16) dst[i + u * stride] = v[u];
-    }
-    const int64_t t = blockIdx.x * int64_t(256) + threadIdx.x;
-    if (t < n_tail) dst_tail[t] = src_tail[t];
-}
-
 struct PackSlot {
     int32_t* host = nullptr;  // pinned
-    int32_t* dptr = nullptr;  // its device address (the pull kernel's source)
+    int32_t* dev = nullptr;   // its device twin (cap words): what the gather and the step read
     size_t thp_bytes = 0;     // a 2 MiB-aligned registered mapping of this size
-    hipEvent_t copied = nullptr;
     int64_t batch = -1;
     int64_t hop_sizes[4 * GS_MAX_HOPS];
     int64_t offsets[GS_MAX_HOPS * GS_PK_NFIELDS];
@@ -98,7 +86,11 @@ struct SamplerStream {
     std::vector<int64_t> batches;  // global batch indices, in order
     std::vector<PackSlot> slots;
     std::deque<int> free, ready;  // guarded by mu
-    std::deque<int> copying;      // driver-only: consumed, H2D copy in flight
+    struct Consumed {
+        int slot;
+        int64_t batch;
+    };
+    std::deque<Consumed> copying;  // driver-only: slots whose step is issued and may still read the twin
     std::mutex mu;
     std::condition_variable cv;
     std::thread th;
@@ -137,21 +129,25 @@ struct gs_runner {
     // trainer took the one-piece path, so the runner reduces W1 itself)
     hipEvent_t w1_ready = nullptr;
     int w1_issued = 0;
-    // Ring of 3 per batch in flight (b % 3): device pack buffer, trainer
-    // gather slot, events.  The side stream pulls batch b's pack and gathers
-    // its layer 1 (reads only X and the pack) while the main stream runs
+    // Ring of 3 per batch in flight (b % 3): trainer gather slot, events.
+    // The side stream gathers batch b's layer 1 (reads only X and the pack's
+    // device twin, complete before its slot was offered) while the main stream runs
     // batch b-1.  No stream ever waits on another's event (a cross-queue wait
     // measured ~17 us of idle GPU here): the host checks instead that the step
     // three batches back released the ring entry, and that the gather of the
     // batch it is about to issue has completed.
     static constexpr int kDev = 3;
-    // Device pack buffers: one per gather-ring entry (b % kDev); entry k's
-    // previous user, step b-3, is the one wait_entry(k) waits for.
-    static constexpr int kPack = kDev;
-    int32_t* dev[kPack] = {};
-    gs::Inflight pulled_slot[kPack];       // sampler stream + slot of the pack in entry p
+    // Host sampler: the packs reach the device from the sampler threads, one
+    // hipMemcpyAsync per batch on this stream (the copy engine), each waited
+    // for by its thread (hipStreamSynchronize: a later thread's copy on the
+    // same stream may be waited for too, a few microseconds).
+    hipStream_t copy_stream = nullptr;
     hipEvent_t dev_done[kDev] = {};        // main: step of the batch in entry k finished
-    bool dev_busy[kDev] = {};
+    bool dev_busy[kDev] = {};              // dev_done[k] is recorded for entry_batch[k]
+    int64_t entry_batch[kDev] = {-1, -1, -1};  // the batch whose step last used entry k
+    // every step <= done_upto has finished reading its ring entry and its pack
+    // (steps finish in order on one stream, so one mark serves all of them)
+    int64_t done_upto = -1;
     // Step completion without an event between steps: the step's SGD launch
     // (with a deferred update: its last slab sum) stores its batch index into done_host (fine-grained pinned memory) when
     // it starts, i.e. once every launch that reads the step's ring entry has
@@ -161,32 +157,59 @@ struct gs_runner {
     int64_t* done_host = nullptr;          // hipHostMalloc, coherent
     int64_t* done_dev = nullptr;
     int64_t flag_step[kDev] = {-1, -1, -1};  // batch whose SGD signals entry k free (-1: none pending)
+    void wait_flag(int64_t want) {
+        const auto t0 = std::chrono::steady_clock::now();
+        for (uint64_t spin = 0; __atomic_load_n(done_host, __ATOMIC_ACQUIRE) < want; ++spin) {
+            __builtin_ia32_pause();
+            // offer the core to runnable sampler threads every 64 polls
+            // while the step runs (the runner is two steps ahead, so a few
+            // microseconds of reaction cost nothing; profiles/r04f_runner_yield_ab.txt)
+            if ((spin & 63) == 63) sched_yield();
+            if ((spin & 0xfffff) == 0xfffff && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(5)) {
+                // no progress for 5 s: let the runtime report a device error, then give up
+                gs::hip_ok(hipDeviceSynchronize(), "hipDeviceSynchronize");
+                if (__atomic_load_n(done_host, __ATOMIC_ACQUIRE) < want)
+                    gs::fail(GS_EHIP, "runner: step completion flag never arrived");
+            }
+        }
+        done_upto = std::max(done_upto, want);
+    }
     void wait_entry(int k) {
         if (flag_step[k] >= 0) {
-            const int64_t want = flag_step[k];
-            const auto t0 = std::chrono::steady_clock::now();
-            for (uint64_t spin = 0; __atomic_load_n(done_host, __ATOMIC_ACQUIRE) < want; ++spin) {
-                __builtin_ia32_pause();
-                // offer the core to runnable sampler threads every 64 polls
-                // while the step runs (the runner is two steps ahead, so a few
-                // microseconds of reaction cost nothing; profiles/r04f_runner_yield_ab.txt)
-                if ((spin & 63) == 63) sched_yield();
-                if ((spin & 0xfffff) == 0xfffff &&
-                    std::chrono::steady_clock::now() - t0 > std::chrono::seconds(5)) {
-                    // no progress for 5 s: let the runtime report a device error, then give up
-                    gs::hip_ok(hipDeviceSynchronize(), "hipDeviceSynchronize");
-                    if (__atomic_load_n(done_host, __ATOMIC_ACQUIRE) < want)
-                        gs::fail(GS_EHIP, "runner: step completion flag never arrived");
-                }
-            }
+            wait_flag(flag_step[k]);
             flag_step[k] = -1;
         }
         if (dev_busy[k]) gs::hip_ok(hipEventSynchronize(dev_done[k]), "hipEventSynchronize");
+        done_upto = std::max(done_upto, entry_batch[k]);
     }
-    hipEvent_t gathered[kDev] = {};        // side: pull + gather of the batch in entry k
+    // Has step b finished reading its ring entry and its pack?  `block`: wait for it.
+    bool step_done(int64_t b, bool block) {
+        if (b <= done_upto) return true;
+        if (use_flag) {
+            const int64_t seen = __atomic_load_n(done_host, __ATOMIC_ACQUIRE);
+            if (seen >= b) {
+                done_upto = std::max(done_upto, seen);
+                return true;
+            }
+        }
+        const int k = static_cast<int>(b % kDev);
+        if (dev_busy[k] && entry_batch[k] >= b) {
+            const hipError_t e = block ? hipEventSynchronize(dev_done[k]) : hipEventQuery(dev_done[k]);
+            if (e == hipErrorNotReady) return false;
+            gs::hip_ok(e, "step event");
+            done_upto = std::max(done_upto, entry_batch[k]);
+            return true;
+        }
+        if (!block) return false;
+        // no event behind this step: its SGD launch signals through the flag
+        GS_REQUIRE(use_flag && flag_step[k] >= b, GS_EINVAL, "runner: a consumed slot's step signals nowhere");
+        wait_flag(b);
+        return true;
+    }
+    hipEvent_t gathered[kDev] = {};        // side: gather of the batch in entry k
     hipStream_t side = nullptr;
     gs::Inflight inflight[kDev];
-    int64_t issued = 0;                    // batches whose pull + gather are issued
+    int64_t issued = 0;                    // batches whose gather is issued
     void* ws = nullptr;
     int64_t ws_bytes = 0;
     float* clip_ws = nullptr;
@@ -239,19 +262,16 @@ struct gs_runner {
     void recycle(gs::SamplerStream& s, bool block);
     bool issue(int64_t b, bool block);
     int take_slot(int64_t b, bool block);
-    void pull(int64_t b, int slot_id);
 };
 
-// Hand the slots whose copy has completed back to their sampler; with
-// `block`, wait for the oldest one when none is free yet.
+// Hand the slots whose step has completed (the last reader of the device
+// twin) back to their sampler; with `block`, wait for the oldest one when
+// none is free yet.
 void gs_runner::recycle(gs::SamplerStream& s, bool block) {
     int n_back = 0;
     while (!s.copying.empty()) {
-        const int q = s.copying.front();
-        const hipError_t e = (block && n_back == 0) ? hipEventSynchronize(s.slots[q].copied)
-                                                     : hipEventQuery(s.slots[q].copied);
-        if (e == hipErrorNotReady) break;
-        gs::hip_ok(e, "copy event");
+        const int q = s.copying.front().slot;
+        if (!step_done(s.copying.front().batch, block && n_back == 0)) break;
         s.copying.pop_front();
         {
             std::lock_guard<std::mutex> lk(s.mu);
@@ -263,6 +283,8 @@ void gs_runner::recycle(gs::SamplerStream& s, bool block) {
 }
 
 void gs_runner::sampler_loop(gs::SamplerStream& s) {
+    // this thread issues its packs' copies: HIP calls on the runner's device
+    const hipError_t dev_err = hipSetDevice(device);
     if (cfg.warm) {
         // one throwaway batch from a copy of the stream's rng into a free
         // slot: the context's buffers grow and fault in here, not inside a
@@ -302,8 +324,22 @@ void gs_runner::sampler_loop(gs::SamplerStream& s) {
         slot.status = gs_sample_pack_run_multi_team(cfg.graph, s.rng, roots.data() + b * merge * cfg.batch,
                                                     nb * cfg.batch, cfg.batch, fanouts.data(), cfg.n_hops, cfg.flags,
                                                     slot.host, cap, slot.hop_sizes, slot.offsets, &slot.used, s.team);
-        if (slot.status != GS_OK) slot.error = gs_last_error();
-        slot.sample_s = gs::secs(t0, gs::Clock::now());
+        if (slot.status != GS_OK) {
+            slot.error = gs_last_error();
+        } else {
+            // the pack is final: into its device twin; this thread waits for the copy
+            // engine, so a slot on `ready` has its pack on the device
+            hipError_t e = dev_err;
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(slot.dev, slot.host, static_cast<size_t>(slot.used) * sizeof(int32_t),
+                                   hipMemcpyHostToDevice, copy_stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(copy_stream);
+            if (e != hipSuccess) {
+                slot.status = GS_EHIP;
+                slot.error = std::string("runner: pack copy to the device: ") + hipGetErrorString(e);
+            }
+        }
+        slot.sample_s = gs::secs(t0, gs::Clock::now());  // the copy call's host time included
         {
             std::lock_guard<std::mutex> lk(s.mu);
             s.ready.push_back(slot_id);
@@ -340,23 +376,6 @@ int gs_runner::take_slot(int64_t b, bool block) {
     GS_REQUIRE(slot.batch == b, GS_EINVAL, "sampler ring out of order");
     if (slot.status != GS_OK) fail(slot.status, slot.error);
     return slot_id;
-}
-
-// Batch b's pack: pinned slot -> device pack entry b % kPack on the side
-// stream (a kernel reading the mapped slot; the copy engine measured no
-// faster).  The entry's previous user, step b - kPack, must have completed.
-void gs_runner::pull(int64_t b, int slot_id) {
-    using namespace gs;
-    PackSlot& slot = streams[b % cfg.n_streams]->slots[slot_id];
-    int32_t* d = dev[b % kPack];
-    const int64_t n16 = slot.used / 4, tail = slot.used - 4 * n16;
-    const int64_t blocks = std::max<int64_t>(1, (n16 + 255) / 256);
-    pull_pack_kernel<<<dim3(static_cast<unsigned>(blocks)), 256, 0, side>>>(
-        reinterpret_cast<const int4*>(slot.dptr), reinterpret_cast<int4*>(d), n16, slot.dptr + 4 * n16, d + 4 * n16,
-        static_cast<int>(tail));
-    hip_ok(hipGetLastError(), "pull_pack_kernel");
-    hip_ok(hipEventRecord(slot.copied, side), "hipEventRecord");
-    pulled_slot[b % kPack] = {static_cast<int>(b % cfg.n_streams), slot_id};
 }
 
 // Device sampler: enqueue stream w's next batches, up to dev_depth queued.
@@ -446,8 +465,9 @@ void gs_runner::dev_sync_rngs() {
     }
 }
 
-// Pull batch b's pack to the device and gather its layer 1, both on the side
-// stream.  block == false: return false if b is not sampled yet.
+// Gather batch b's layer 1 from its pack's device twin (filled by its
+// sampler thread) on the side stream.  block == false: return false if b is
+// not sampled yet.
 bool gs_runner::issue(int64_t b, bool block) {
     using namespace gs;
     int slot_id = -1;
@@ -473,10 +493,11 @@ bool gs_runner::issue(int64_t b, bool block) {
         dev_enqueue(static_cast<int>(b % cfg.n_streams));
         return true;
     }
-    pull(b, slot_id);
-    const Inflight f = pulled_slot[b % kPack];
+    const Inflight f{static_cast<int>(b % cfg.n_streams), slot_id};
     PackSlot& slot = streams[f.stream]->slots[f.slot];
-    const int rc = gs_trainer_gather(cfg.trainer, dev[b % kPack], slot.hop_sizes, slot.offsets, k, side);
+    // the twin holds the pack since before the slot came onto `ready`; the
+    // step's launches read it after this gather, both until the step is done
+    const int rc = gs_trainer_gather(cfg.trainer, slot.dev, slot.hop_sizes, slot.offsets, k, side);
     if (rc != GS_OK) fail(rc, gs_last_error());
     hip_ok(hipEventRecord(gathered[k], side), "hipEventRecord");
     inflight[k] = f;
@@ -509,10 +530,12 @@ gs_runner::~gs_runner() {
     for (auto& s : streams)
         if (s->th.joinable()) s->th.join();
     for (auto& s : streams) gs_team_destroy(s->team);
-    // Device work that may still read the pinned slots or the device rings:
-    // the side stream (pull kernels of consumed and of issued-but-unconsumed
+    // Device work that may still read the pinned slots, their device twins
+    // or the device rings: the copy stream (no sampler thread is left to add
+    // to it), the side stream (gathers of consumed and of issued-but-unconsumed
     // lookahead batches), the steps in flight and the comm stream.  Drain all
     // of it before any buffer is freed.
+    if (copy_stream) (void)hipStreamSynchronize(copy_stream);
     if (side) (void)hipStreamSynchronize(side);
     if (comm_stream) (void)hipStreamSynchronize(comm_stream);
     for (int d = 0; d < kDev; ++d)
@@ -520,19 +543,14 @@ gs_runner::~gs_runner() {
     if (done_host) (void)hipHostFree(done_host);
     for (auto& s : streams)
         for (auto& slot : s->slots) {
-            if (slot.copied) {
-                (void)hipEventSynchronize(slot.copied);
-                (void)hipEventDestroy(slot.copied);
-            }
             if (slot.host && slot.thp_bytes) {
                 (void)hipHostUnregister(slot.host);
                 munmap(slot.host, slot.thp_bytes);
             } else if (slot.host) {
                 (void)hipHostFree(slot.host);
             }
+            if (slot.dev) (void)hipFree(slot.dev);
         }
-    for (int d = 0; d < kPack; ++d)
-        if (dev[d]) (void)hipFree(dev[d]);
     for (int32_t* p : dpack)
         if (p) (void)hipFree(p);
     if (roots_dev) (void)hipFree(roots_dev);
@@ -549,6 +567,7 @@ gs_runner::~gs_runner() {
     if (upper_reduced) (void)hipEventDestroy(upper_reduced);
     if (comm_stream) (void)hipStreamDestroy(comm_stream);
     if (side) (void)hipStreamDestroy(side);
+    if (copy_stream) (void)hipStreamDestroy(copy_stream);
     if (ws) (void)hipFree(ws);
     if (clip_ws) (void)hipFree(clip_ws);
 }
@@ -623,7 +642,7 @@ int gs_runner_create(const gs_runner_config* cfg, gs_runner** out) {
     GS_REQUIRE(bound > 0, GS_EINVAL, "pack bound failed");
     r->cap = bound + mb;
     hip_ok(hipGetDevice(&r->device), "hipGetDevice");
-    {  // high priority: the side stream's pull + gather dispatch ahead of the step they overlap
+    {  // high priority: the side stream's gather dispatches ahead of the step it overlaps
         int lo = 0, hi = 0;
         hip_ok(hipDeviceGetStreamPriorityRange(&lo, &hi), "hipDeviceGetStreamPriorityRange");
         hip_ok(hipStreamCreateWithPriority(&r->side, hipStreamNonBlocking, hi), "hipStreamCreateWithPriority");
@@ -632,8 +651,6 @@ int gs_runner_create(const gs_runner_config* cfg, gs_runner** out) {
         hip_ok(hipEventCreateWithFlags(&r->dev_done[d], sync_event_flags()), "hipEventCreate");
         hip_ok(hipEventCreateWithFlags(&r->gathered[d], sync_event_flags()), "hipEventCreate");
     }
-    for (int d = 0; d < gs_runner::kPack; ++d)
-        hip_ok(hipMalloc(&r->dev[d], r->cap * sizeof(int32_t)), "hipMalloc(pack)");
     hip_ok(hipMalloc(&r->clip_ws, 64 * 8 * sizeof(float)), "hipMalloc(clip ws)");
     r->use_flag = !cfg->embed_out;
     if (r->use_flag) {
@@ -732,9 +749,9 @@ int gs_runner_create(const gs_runner_config* cfg, gs_runner** out) {
     // idle) instead of helpers private to each stream.
     const char* shared_env = std::getenv("GS_SHARED_HELPERS");
     const bool shared_helpers = shared_env && std::atoi(shared_env) == 1;
-    // pack slots on transparent huge pages: the pull kernel's host reads then
-    // need one translation per 2 MiB instead of per 4 KiB page (pull kernel
-    // 13.26 -> 12.63 us)
+    if (!r->devmode) hip_ok(hipStreamCreateWithFlags(&r->copy_stream, hipStreamNonBlocking), "hipStreamCreate(copy)");
+    // pack slots on transparent huge pages: the device's reads of a slot then
+    // need one translation per 2 MiB instead of per 4 KiB page
     for (int32_t w = 0; w < S && !r->devmode; ++w) {
         auto s = std::make_unique<SamplerStream>();
         s->rng = cfg->rngs[w];
@@ -762,12 +779,9 @@ int gs_runner_create(const gs_runner_config* cfg, gs_runner** out) {
                 std::memset(reinterpret_cast<void*>(a), 0, bytes);
                 sl.host = reinterpret_cast<int32_t*>(a);
                 sl.thp_bytes = bytes;
-                hip_ok(hipHostRegister(sl.host, bytes, hipHostRegisterMapped), "hipHostRegister(pack slot)");
-                void* dp = nullptr;
-                hip_ok(hipHostGetDevicePointer(&dp, sl.host, 0), "hipHostGetDevicePointer");
-                sl.dptr = static_cast<int32_t*>(dp);
+                hip_ok(hipHostRegister(sl.host, bytes, hipHostRegisterDefault), "hipHostRegister(pack slot)");
             }
-            hip_ok(hipEventCreateWithFlags(&s->slots[q].copied, sync_event_flags()), "hipEventCreate");
+            hip_ok(hipMalloc(&sl.dev, r->cap * sizeof(int32_t)), "hipMalloc(pack twin)");
             s->free.push_back(q);
         }
         r->streams.push_back(std::move(s));
@@ -883,7 +897,7 @@ int gs_runner_run(gs_runner* r, int64_t n_steps, float* loss, void* stream) {
             ++r->stats.lookahead_misses;
             r->issue(b, true);
         }
-        // look ahead: batch b+1's pull + gather run on the side stream under
+        // look ahead: batch b+1's gather runs on the side stream under
         // this step (never block here: with a slow sampler that would idle the GPU)
         if (b + 1 < r->n_units && r->issued == b + 1) r->issue(b + 1, false);
         const int k = static_cast<int>(b % gs_runner::kDev);
@@ -921,7 +935,7 @@ int gs_runner_run(gs_runner* r, int64_t n_steps, float* loss, void* stream) {
         }
         const int64_t pack_total = used - r->cfg.batch;
         bool consumed_flag = false;
-        int32_t* pk = r->devmode ? r->dpack[f.slot] : r->dev[b % gs_runner::kPack];
+        int32_t* pk = r->devmode ? r->dpack[f.slot] : r->streams[f.stream]->slots[f.slot].dev;
         auto t3 = Clock::now();
         if (r->cfg.embed_out) {  // inference: the forward into this batch's output rows
             const int rc = gs_trainer_forward_gathered(r->cfg.trainer, pk, hop_sizes, offsets, k, r->ws,
@@ -967,6 +981,7 @@ int gs_runner_run(gs_runner* r, int64_t n_steps, float* loss, void* stream) {
             trainer_set_done(r->cfg.trainer, nullptr, 0);
             if (rc != GS_OK) fail(rc, gs_last_error());
         }
+        r->entry_batch[k] = b;
         if (consumed_flag) {
             r->flag_step[k] = b;  // its SGD signals the entry free
             r->dev_busy[k] = false;
@@ -977,7 +992,7 @@ int gs_runner_run(gs_runner* r, int64_t n_steps, float* loss, void* stream) {
         }
         for (int q = 0; q < 4 * GS_MAX_HOPS; ++q) r->stats.hop_sizes[q] += static_cast<double>(hop_sizes[q]);
         r->stats.sample_s += sample_s;
-        if (!r->devmode) r->streams[f.stream]->copying.push_back(f.slot);
+        if (!r->devmode) r->streams[f.stream]->copying.push_back({f.slot, b});
         ++r->next_batch;
         ++r->stats.steps;
         const auto t4 = Clock::now();

@@ -421,7 +421,8 @@ class Communicator:
 
 class Runner:
     """The training loop as one native pipeline (gs_runner): S sampler
-    threads, pinned pack rings, the next batch's device pull and layer-1
+    threads, pinned pack rings whose slots each have a device twin (the sampler
+    thread copies a finished pack there), the next batch's layer-1
     gather on a high-priority side stream, and the fused
     step, all without Python per step.  `batches`: iterable of equal-size
     int64 root arrays consumed in order; `rngs`: one RNG per sampler stream
@@ -536,7 +537,7 @@ class Runner:
 class Embedder:
     """get_gnn_embeddings (utils.py:59-78) as one native pipeline: the
     training runner in forward-only mode (gs_runner_config.embed_out) over
-    batches of `batch` ids, S sampler streams, the next batch's pull + layer-1
+    batches of `batch` ids, S sampler streams, the next batch's layer-1
     gather under the current forward, embeddings written in place.
 
     `merge` = m consecutive batches share one pack and one forward launch

@@ -694,11 +694,13 @@ int gs_comm_allreduce_sum(void* comm, float* buf, int64_t n, void* stream);
  * The reference's epoch loop over batches (utils.py:144-191 called from
  * main.py per epoch) as a native pipeline: S sampler threads (stream w owns
  * batches w, w+S, ... and its own rng — S = 1 is the reference's single
- * random stream) fill rings of pinned pack buffers with gs_sample_pack_run;
- * gs_runner_run consumes the batches in order, issuing on `stream` the pack's
- * H2D copy (two device buffers, reused in stream order), forward_backward,
- * the optional all-reduce and the update.  Sampler threads make no HIP calls;
- * the calling thread recycles a pinned slot once its copy event completes.
+ * random stream) fill rings of pinned pack buffers with gs_sample_pack_run
+ * and copy each finished pack into its slot's device twin (the copy engine,
+ * on the runner's copy stream, waited for by the sampler thread);
+ * gs_runner_run consumes the batches in order, issuing the layer-1 gather
+ * from the twin on a side stream and on `stream` forward_backward, the
+ * optional all-reduce and the update.  The calling thread hands a slot back
+ * to its sampler once the step that read its twin has completed.
  * The rngs, graph and trainer are borrowed and must outlive the runner;
  * `batches` (n_batches x batch int64 ids) is copied. */
 typedef struct {
@@ -772,7 +774,7 @@ typedef struct {
     double hop_sizes[4 * GS_MAX_HOPS]; /* summed (n_dst, n_pos, n_src, n_nbr) */
     double wait_sample_s;   /* ... on a not-yet-sampled batch */
     double wait_ring_s;     /* ... on the step three batches back (ring entry reuse) */
-    double wait_gather_s;   /* ... on this batch's side-stream pull + gather */
+    double wait_gather_s;   /* ... on this batch's side-stream gather */
     double fwd_bwd_s, update_s; /* parts of issue_s */
     double max_step_s;      /* longest single step (wait + issue) */
     int64_t lookahead_misses; /* steps whose batch was not issued one step ahead */
