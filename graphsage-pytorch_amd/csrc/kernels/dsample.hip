@@ -34,6 +34,7 @@
 
 #include "../host/graph.hpp"
 #include "../host/mt19937.hpp"
+#include "dev_host.hpp"
 #include "dsample.hpp"
 #include "fsample.hpp"
 
@@ -239,10 +240,10 @@ __global__ __launch_bounds__(1024) void hop_setup_kernel(DevGraph g, Ctl* c, Hop
     }
     int cnt_tot, draw_tot;
     float mean_tot, var_tot;
-    int cnt_pre = block_excl_scan(cnt_sum, shi, &cnt_tot);
-    int draw_pre = block_excl_scan(draw_sum, shi, &draw_tot);
-    float mean_pre = block_excl_scan(mean_sum, shf, &mean_tot);
-    float var_pre = block_excl_scan(var_sum, shf, &var_tot);
+    int cnt_pre = block_excl_scan<16>(cnt_sum, shi, &cnt_tot);
+    int draw_pre = block_excl_scan<16>(draw_sum, shi, &draw_tot);
+    float mean_pre = block_excl_scan<16>(mean_sum, shf, &mean_tot);
+    float var_pre = block_excl_scan<16>(var_sum, shf, &var_tot);
     auto place = [&](int r, int32_t d, float2 mv) {
         const bool sampled = k > 0 && d >= k;
         hb.pos_ptr[r] = cnt_pre;
@@ -288,7 +289,7 @@ __global__ __launch_bounds__(1024) void hop_setup_kernel(DevGraph g, Ctl* c, Hop
         int cnt = 0;
         for (int b = b0; b < b1; ++b) cnt += (min(hb.bw[b], kWMax) + kMEntries - 1) / kMEntries;
         int tot;
-        int at = block_excl_scan(cnt, shi, &tot);
+        int at = block_excl_scan<16>(cnt, shi, &tot);
         for (int b = b0; b < b1; ++b) {
             const int parts = (min(hb.bw[b], kWMax) + kMEntries - 1) / kMEntries;
             for (int y = 0; y < parts; ++y) hb.wg[at++] = b | (y << 16);
@@ -933,6 +934,10 @@ __global__ void begin_kernel(Ctl* c, const int32_t* __restrict__ roots, int32_t*
         c->total = 0;
         c->used = 0;
         c->pos_batch = c->pos_cur;
+        // an empty neighbourhood fails its own run only: that run completed and
+        // left the stream where the host sampler's would be (the kStFail
+        // statuses stay until set_rng: their run stopped part-way)
+        c->status &= ~kStEmpty;
         // every run starts on a fresh mark epoch: a union reads epoch + 1 and
         // only finish_union advances it, so a run that failed before its
         // finish_union (kStTable / kStSize / kStSpin, then GS_DS_BAIL) left
@@ -957,12 +962,9 @@ __global__ void copy_block_kernel(const uint32_t* __restrict__ xr, int64_t first
 // --------------------------------------------------------------- host side
 
 using namespace gs::ds;
+using gs::hip_ok;
 
 namespace {
-
-void hip_ok(hipError_t e, const char* what) {
-    if (e != hipSuccess) gs::fail(GS_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-}
 
 int r_of(int k) { return k > 0 ? std::max(1, 256 / k) : 256; }
 
@@ -978,47 +980,32 @@ struct gs_dsampler {
     int64_t npos_max[GS_MAX_HOPS] = {};
     const gs_graph* host_graph = nullptr;
     DevGraph g{};
-    std::vector<void*> owned;
     uint32_t* xr = nullptr;   // raw words ring
     uint32_t* wr = nullptr;   // tempered words ring
     uint32_t* tmp = nullptr;  // small transfer buffer (state block, words)
     int64_t tmp_n = 0;
     Ctl* ctl = nullptr;       // device control block
-    Ctl* ctl_host = nullptr;  // pinned mirrors, run i's copied into slot i % kResSlots at its end
-    hipEvent_t run_done[kResSlots] = {};  // per slot: its run's end
-    int64_t n_runs = 0;
     HopBufs hb[GS_MAX_HOPS];
     UnionBufs ub[GS_MAX_HOPS];
     int32_t* pack_cur = nullptr;
     uint64_t* mark = nullptr;  // first-occurrence marks of the frontier unions (shared by the hops)
     int32_t* lid = nullptr;    // union key -> frontier position (shared by the hops)
-    hipEvent_t done = nullptr;
     hipStream_t last_stream = nullptr;
     // aux stream: the union's lists and the next run's words beside the
     // draws (GS_DS_AUX=0: everything on the caller's stream)
     hipStream_t aux = nullptr;
     hipEvent_t ev_gen = nullptr, ev_join = nullptr;
-    bool ran = false;
+    // freed after the destructor's waits: ring first (declared last), then mem
+    gs::DevArena mem{"dsampler"};
+    gs::RunRing<Ctl> ring;
 
-    template <typename T>
-    T* alloc(int64_t n) {
-        void* p = nullptr;
-        hip_ok(hipMalloc(&p, std::max<int64_t>(n, 1) * sizeof(T)), "hipMalloc(dsampler)");
-        owned.push_back(p);
-        return static_cast<T*>(p);
-    }
     ~gs_dsampler() {
         if (fast) gs::fs::fast_destroy(fast);
-        if (done) (void)hipEventSynchronize(done);
+        (void)ring.wait_last_if_any();
         if (aux) (void)hipStreamSynchronize(aux);
         for (hipEvent_t e : {ev_gen, ev_join})
             if (e) (void)hipEventDestroy(e);
         if (aux) (void)hipStreamDestroy(aux);
-        for (void* p : owned) (void)hipFree(p);
-        if (ctl_host) (void)hipHostFree(ctl_host);
-        for (hipEvent_t e : run_done)
-            if (e) (void)hipEventDestroy(e);
-        if (done) (void)hipEventDestroy(done);
     }
 };
 
@@ -1073,7 +1060,7 @@ void launch_hop_draws(gs_dsampler* ds, int hop, bool last, int n_roots, hipStrea
 
 void ensure_tmp(gs_dsampler* ds, int64_t n) {
     if (ds->tmp_n >= n) return;
-    ds->tmp = ds->alloc<uint32_t>(n);
+    ds->tmp = ds->mem.alloc<uint32_t>(n);
     ds->tmp_n = n;
 }
 
@@ -1106,20 +1093,7 @@ void check_status(int status) {
 namespace gs {
 bool dsampler_run_ready(gs_dsampler* ds, int64_t run) {
     if (ds && ds->fast) return gs::fs::fast_run_ready(ds->fast, run);
-    if (!ds || run < ds->n_runs - kResSlots) return true;
-    if (run >= ds->n_runs) return false;
-    const hipError_t e = hipEventQuery(ds->run_done[run % kResSlots]);
-    if (e == hipErrorNotReady) return false;
-    hip_ok(e, "hipEventQuery(dsampler run)");
-    return true;
-}
-bool dsampler_ready(gs_dsampler* ds) {
-    if (ds && ds->fast) return gs::fs::fast_run_ready(ds->fast, -1);
-    if (!ds || !ds->ran) return true;
-    const hipError_t e = hipEventQuery(ds->done);
-    if (e == hipErrorNotReady) return false;
-    hip_ok(e, "hipEventQuery(dsampler)");
-    return true;
+    return !ds || ds->ring.ready(run);
 }
 }  // namespace gs
 
@@ -1159,73 +1133,62 @@ int gs_dsampler_create(const gs_graph* gp, const int32_t* fanouts, int32_t n_hop
         nd = std::min<int64_t>(g.n_nodes, nd + nd * per);
     }
     // graph
-    auto up = [&](const void* src, size_t bytes) {
-        void* p = nullptr;
-        hip_ok(hipMalloc(&p, std::max<size_t>(bytes, 1)), "hipMalloc(graph)");
-        ds->owned.push_back(p);
-        if (bytes) hip_ok(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice), "hipMemcpy(graph)");
-        return p;
-    };
+    auto up = [&](const void* src, size_t bytes) { return ds->mem.upload(src, bytes); };
     ds->g.n_nodes = g.n_nodes;
     ds->g.row_ptr = static_cast<const int64_t*>(up(g.row_ptr.data(), g.row_ptr.size() * sizeof(int64_t)));
     ds->g.col = static_cast<const int32_t*>(up(g.col.data(), g.col.size() * sizeof(int32_t)));
     ds->g.slot = static_cast<const uint32_t*>(up(g.slot.data(), g.slot.size() * sizeof(uint32_t)));
     ds->g.log2size = static_cast<const uint8_t*>(up(g.log2size.data(), g.log2size.size()));
     ds->g.dirty = g.dirty.empty() ? nullptr : static_cast<const uint8_t*>(up(g.dirty.data(), g.dirty.size()));
-    ds->xr = ds->alloc<uint32_t>(kRing);
-    ds->wr = ds->alloc<uint32_t>(kRing);
-    ds->ctl = ds->alloc<Ctl>(1);
+    ds->xr = ds->mem.alloc<uint32_t>(kRing);
+    ds->wr = ds->mem.alloc<uint32_t>(kRing);
+    ds->ctl = ds->mem.alloc<Ctl>(1);
     hip_ok(hipMemset(ds->ctl, 0, sizeof(Ctl)), "hipMemset");
-    hip_ok(hipHostMalloc(reinterpret_cast<void**>(&ds->ctl_host), kResSlots * sizeof(Ctl), hipHostMallocDefault),
-           "hipHostMalloc");
-    std::memset(ds->ctl_host, 0, kResSlots * sizeof(Ctl));
-    for (hipEvent_t& e : ds->run_done) hip_ok(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
     for (int32_t j = 0; j < n_hops; ++j) {
         const int k = ds->fanouts[j];
         const int64_t ndj = ds->nd_max[j];
         const int64_t nb = (ndj + r_of(k) - 1) / r_of(k);
         const int64_t ng = (nb + kMinG - 1) / kMinG;
         HopBufs& h = ds->hb[j];
-        h.dst = ds->alloc<int32_t>(ndj);
-        h.deg = ds->alloc<int32_t>(ndj);
-        h.mv = ds->alloc<float2>(ndj);
-        h.pos_ptr = ds->alloc<int32_t>(ndj + 1);
-        h.blo = ds->alloc<int32_t>(nb + 1);
-        h.bw = ds->alloc<int32_t>(nb + 1);
-        h.dbase = ds->alloc<int32_t>(nb + 1);
-        h.tab = ds->alloc<uint16_t>(nb * kWMax);
-        h.path = ds->alloc<int32_t>(nb * kWMax);
-        h.gexit = ds->alloc<uint16_t>(ng * kWMax);
-        h.gexit_last = ds->alloc<int32_t>(kWMax);
-        h.entry = ds->alloc<int32_t>(nb);
-        h.rej = ds->alloc<uint8_t>(nb * r_of(k) * kWMax);
-        h.wg = ds->alloc<int32_t>(nb * (kWMax / kMEntries));
-        h.ent = j + 1 < n_hops ? ds->alloc<int32_t>(ds->npos_max[j]) : nullptr;
+        h.dst = ds->mem.alloc<int32_t>(ndj);
+        h.deg = ds->mem.alloc<int32_t>(ndj);
+        h.mv = ds->mem.alloc<float2>(ndj);
+        h.pos_ptr = ds->mem.alloc<int32_t>(ndj + 1);
+        h.blo = ds->mem.alloc<int32_t>(nb + 1);
+        h.bw = ds->mem.alloc<int32_t>(nb + 1);
+        h.dbase = ds->mem.alloc<int32_t>(nb + 1);
+        h.tab = ds->mem.alloc<uint16_t>(nb * kWMax);
+        h.path = ds->mem.alloc<int32_t>(nb * kWMax);
+        h.gexit = ds->mem.alloc<uint16_t>(ng * kWMax);
+        h.gexit_last = ds->mem.alloc<int32_t>(kWMax);
+        h.entry = ds->mem.alloc<int32_t>(nb);
+        h.rej = ds->mem.alloc<uint8_t>(nb * r_of(k) * kWMax);
+        h.wg = ds->mem.alloc<int32_t>(nb * (kWMax / kMEntries));
+        h.ent = j + 1 < n_hops ? ds->mem.alloc<int32_t>(ds->npos_max[j]) : nullptr;
         if (j + 1 < n_hops) {
             GS_REQUIRE(k >= 1, GS_EINVAL, "device sampler: hops before the last need a fanout >= 1");
             UnionBufs& u = ds->ub[j];
-            u.set_cnt = ds->alloc<int32_t>(ndj);
-            u.set_items = ds->alloc<int32_t>(ds->npos_max[j] + ndj);
-            u.first_tab = ds->alloc<int32_t>(kSmallSet);
-            u.first_meta = ds->alloc<int32_t>(2);
-            u.tpre = ds->alloc<int32_t>(ndj + 1);
-            u.ubef = ds->alloc<int32_t>(ndj + 1);
-            u.fresh = ds->alloc<int32_t>(ds->npos_max[j] + ndj);
-            u.tcnt = ds->alloc<int32_t>(ds->nd_max[j + 1] + 1);
-            u.longs = ds->alloc<int32_t>(ds->nd_max[j + 1] + 1);
-            u.fmask = ds->alloc<uint64_t>(ndj);
-            u.sched = ds->alloc<int32_t>(2 * (kMaxStages + 1));
-            u.skeys = ds->alloc<int32_t>(2 * static_cast<int64_t>(kBigKeys));
+            u.set_cnt = ds->mem.alloc<int32_t>(ndj);
+            u.set_items = ds->mem.alloc<int32_t>(ds->npos_max[j] + ndj);
+            u.first_tab = ds->mem.alloc<int32_t>(kSmallSet);
+            u.first_meta = ds->mem.alloc<int32_t>(2);
+            u.tpre = ds->mem.alloc<int32_t>(ndj + 1);
+            u.ubef = ds->mem.alloc<int32_t>(ndj + 1);
+            u.fresh = ds->mem.alloc<int32_t>(ds->npos_max[j] + ndj);
+            u.tcnt = ds->mem.alloc<int32_t>(ds->nd_max[j + 1] + 1);
+            u.longs = ds->mem.alloc<int32_t>(ds->nd_max[j + 1] + 1);
+            u.fmask = ds->mem.alloc<uint64_t>(ndj);
+            u.sched = ds->mem.alloc<int32_t>(2 * (kMaxStages + 1));
+            u.skeys = ds->mem.alloc<int32_t>(2 * static_cast<int64_t>(kBigKeys));
             if (!ds->mark) {
-                ds->mark = ds->alloc<uint64_t>(g.n_nodes);
+                ds->mark = ds->mem.alloc<uint64_t>(g.n_nodes);
                 hip_ok(hipMemset(ds->mark, 0, g.n_nodes * sizeof(uint64_t)), "hipMemset(mark)");
-                ds->lid = ds->alloc<int32_t>(g.n_nodes);
+                ds->lid = ds->mem.alloc<int32_t>(g.n_nodes);
             }
             u.mark = ds->mark;
             u.lid = ds->lid;
         }
     }
-    hip_ok(hipEventCreateWithFlags(&ds->done, hipEventDisableTiming), "hipEventCreate");
     const char* aux_env = std::getenv("GS_DS_AUX");
     if (!(flags & GS_DSAMPLER_NO_AUX) && !(aux_env && std::string(aux_env) == "0")) {
         hip_ok(hipStreamCreateWithFlags(&ds->aux, hipStreamNonBlocking), "hipStreamCreate(dsampler aux)");
@@ -1249,7 +1212,7 @@ int gs_dsampler_set_rng(gs_dsampler* ds, const uint32_t* mt624, int64_t pos, voi
     GS_REQUIRE(!ds->fast, GS_EINVAL, "a GS_DSAMPLER_FAST handle has no MT19937 stream");
     GS_REQUIRE(pos >= 0 && pos <= 624, GS_EINVAL, "state index out of range");
     hipStream_t st = gs::as_stream(stream);
-    if (ds->ran) hip_ok(hipEventSynchronize(ds->done), "hipEventSynchronize");
+    hip_ok(ds->ring.wait_last_if_any(), "hipEventSynchronize");
     ensure_tmp(ds, 624);
     hip_ok(hipMemcpyAsync(ds->tmp, mt624, 624 * sizeof(uint32_t), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
     mt_seed_kernel<<<1, 256, 0, st>>>(ds->tmp, pos, ds->xr, ds->wr, ds->ctl);
@@ -1263,7 +1226,7 @@ int gs_dsampler_get_rng(gs_dsampler* ds, uint32_t* mt624, int64_t* pos, void* st
     GS_REQUIRE(ds && mt624 && pos, GS_EINVAL, "NULL argument");
     GS_REQUIRE(!ds->fast, GS_EINVAL, "a GS_DSAMPLER_FAST handle has no MT19937 stream");
     hipStream_t st = gs::as_stream(stream);
-    if (ds->ran) hip_ok(hipEventSynchronize(ds->done), "hipEventSynchronize");
+    hip_ok(ds->ring.wait_last_if_any(), "hipEventSynchronize");
     const int64_t p = pos_now(ds, st);
     int64_t blk = p / 624, idx = p % 624;
     if (p > 0 && idx == 0) {
@@ -1286,7 +1249,7 @@ int gs_dsampler_words(gs_dsampler* ds, int64_t n, uint32_t* out, void* stream) {
     GS_REQUIRE(ds && out && n >= 0 && n < kRing / 2, GS_EINVAL, "bad arguments");
     GS_REQUIRE(!ds->fast, GS_EINVAL, "a GS_DSAMPLER_FAST handle has no MT19937 stream");
     hipStream_t st = gs::as_stream(stream);
-    if (ds->ran) hip_ok(hipEventSynchronize(ds->done), "hipEventSynchronize");
+    hip_ok(ds->ring.wait_last_if_any(), "hipEventSynchronize");
     const int64_t p = pos_now(ds, st);
     mt_gen_kernel<<<1, kGenThreads, 0, st>>>(ds->xr, ds->wr, ds->ctl, p + n, -1);
     gs::check_launch("mt_gen_kernel");
@@ -1328,46 +1291,16 @@ int gs_dsampler_run(gs_dsampler* ds, const int32_t* roots, int64_t n_roots, int3
     finish_kernel<<<8, 256, 0, st>>>(ds->ctl, roots, static_cast<int>(n_roots), pack,
                                      (ds->flags & GS_SAMPLE_FAIL_EMPTY) ? 1 : 0, ds->n_hops);
     gs::check_launch("finish_kernel");
-    const int slot = static_cast<int>(ds->n_runs % kResSlots);
-    hip_ok(hipMemcpyAsync(ds->ctl_host + slot, ds->ctl, sizeof(Ctl), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(ctl)");
-    hip_ok(hipEventRecord(ds->run_done[slot], st), "hipEventRecord");
-    hip_ok(hipEventRecord(ds->done, st), "hipEventRecord");
-    ds->ran = true;
-    ++ds->n_runs;
+    ds->ring.record(ds->ctl, st);
     GS_API_END
 }
 
 int gs_dsampler_debug(gs_dsampler* ds, int64_t* out, int32_t n) {
     GS_API_BEGIN
-    GS_REQUIRE(ds && !ds->fast && ds->ran && out && n >= 0 && n <= 64, GS_EINVAL, "bad arguments");
-    hip_ok(hipEventSynchronize(ds->done), "hipEventSynchronize");
-    std::memcpy(out, ds->ctl_host[(ds->n_runs - 1) % kResSlots].dbg, n * sizeof(int64_t));
+    GS_REQUIRE(ds && !ds->fast && ds->ring.runs() && out && n >= 0 && n <= 64, GS_EINVAL, "bad arguments");
+    std::memcpy(out, ds->ring.wait(-1).dbg, n * sizeof(int64_t));
     GS_API_END
 }
-
-namespace {
-// The layout of the run whose Ctl mirror is `c`, as the host sampler reports it.
-void report(const gs_dsampler* ds, const Ctl& c, int64_t* hop_sizes, int64_t* offsets, int64_t* used) {
-    check_status(c.status);
-    for (int32_t j = 0; j < GS_MAX_HOPS; ++j) {
-        const bool on = j < ds->n_hops;
-        const bool last = j == ds->n_hops - 1;
-        if (hop_sizes) {
-            hop_sizes[4 * j] = on ? c.hop[j].n_dst : 0;
-            hop_sizes[4 * j + 1] = on ? c.hop[j].n_pos : 0;
-            // as the host sampler: -1 = not materialised (the last hop), 0 past the hops
-            hop_sizes[4 * j + 2] = on ? (last ? -1 : c.hop[j].n_src) : 0;
-            hop_sizes[4 * j + 3] = on ? (last ? -1 : c.hop[j].n_nbr) : 0;
-        }
-        if (offsets)
-            for (int f = 0; f < GS_PK_NFIELDS; ++f) {
-                const bool lastf = f == GS_PK_POS_PTR || f == GS_PK_POS || f == GS_PK_DST_IDS;
-                offsets[j * GS_PK_NFIELDS + f] = on && (last == lastf) ? c.hop[j].off[f] : -1;
-            }
-    }
-    if (used) *used = c.used;
-}
-}  // namespace
 
 int gs_dsampler_result(gs_dsampler* ds, int64_t* hop_sizes, int64_t* offsets, int64_t* used) {
     GS_API_BEGIN
@@ -1376,15 +1309,15 @@ int gs_dsampler_result(gs_dsampler* ds, int64_t* hop_sizes, int64_t* offsets, in
         gs::fs::fast_result_of(ds->fast, -1, hop_sizes, offsets, used);
         return GS_OK;
     }
-    GS_REQUIRE(ds->ran, GS_EINVAL, "no run to report");
-    hip_ok(hipEventSynchronize(ds->done), "hipEventSynchronize");
-    report(ds, ds->ctl_host[(ds->n_runs - 1) % kResSlots], hop_sizes, offsets, used);
+    const Ctl& c = ds->ring.wait(-1);
+    check_status(c.status);
+    gs::report_layout(c, ds->n_hops, hop_sizes, offsets, used);
     GS_API_END
 }
 
 int64_t gs_dsampler_runs(const gs_dsampler* ds) {
     if (ds && ds->fast) return gs::fs::fast_runs(ds->fast);
-    return ds ? ds->n_runs : -1;
+    return ds ? ds->ring.runs() : -1;
 }
 
 int gs_dsampler_set_seed(gs_dsampler* ds, uint64_t seed) {
@@ -1405,17 +1338,14 @@ int gs_dsampler_run_at(gs_dsampler* ds, int64_t batch_index, const int32_t* root
 int gs_dsampler_result_of(gs_dsampler* ds, int64_t run, int64_t* hop_sizes, int64_t* offsets, int64_t* used) {
     GS_API_BEGIN
     GS_REQUIRE(ds, GS_EINVAL, "NULL argument");
+    GS_REQUIRE(run >= 0, GS_ERANGE, "device sampler: run not issued");
     if (ds->fast) {
-        GS_REQUIRE(run >= 0, GS_ERANGE, "device sampler: run not issued");
         gs::fs::fast_result_of(ds->fast, run, hop_sizes, offsets, used);
         return GS_OK;
     }
-    GS_REQUIRE(run >= 0 && run < ds->n_runs && run >= ds->n_runs - kResSlots, GS_ERANGE,
-               "device sampler: run not issued or no longer kept (the last " + std::to_string(kResSlots) +
-                   " runs are)");
-    const int slot = static_cast<int>(run % kResSlots);
-    hip_ok(hipEventSynchronize(ds->run_done[slot]), "hipEventSynchronize");
-    report(ds, ds->ctl_host[slot], hop_sizes, offsets, used);
+    const Ctl& c = ds->ring.wait(run);
+    check_status(c.status);
+    gs::report_layout(c, ds->n_hops, hop_sizes, offsets, used);
     GS_API_END
 }
 

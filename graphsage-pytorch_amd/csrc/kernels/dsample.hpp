@@ -2,6 +2,7 @@
 // dsample_union.hip (per-node sets, the frontier union and the lists).
 #pragma once
 
+#include "block_scan.hpp"
 #include "kcommon.hpp"
 
 namespace gs {
@@ -15,7 +16,6 @@ constexpr int kMinG = kComposeEntries / kWMax;
 constexpr int kChainEntries = 30720;         // group exits the chain block stages in LDS (uint16)
 constexpr int kMaxGroups = 1024;
 constexpr int kMEntries = 256;               // window entries per table-kernel workgroup
-constexpr int kResSlots = 4;                 // runs whose results are kept (gs_dsampler_result_of)
 
 // status bits (Ctl::status)
 constexpr int kStWindow = 1;   // a true entry fell outside its block window
@@ -125,50 +125,6 @@ constexpr int kUnionMax = 16384;    // table slots of a frontier union in LDS (u
 constexpr int kUnionBig = 65536;    // ... with uint16 priorities, keys in global memory (ubig_kernel)
 constexpr int kBigKeys = kUnionBig * 3 / 5 + 1024;  // a big stage's keys (its table <= 3/5 full)
 constexpr int kMaxStages = 24;
-
-
-__device__ __forceinline__ int warp_incl_scan(int v) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o, 64);
-        if ((threadIdx.x & 63) >= o) v += t;
-    }
-    return v;
-}
-__device__ __forceinline__ float warp_incl_scan(float v) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float t = __shfl_up(v, o, 64);
-        if ((threadIdx.x & 63) >= o) v += t;
-    }
-    return v;
-}
-
-// Exclusive scan over a 1024-thread block of one value per thread; returns
-// the thread's exclusive prefix, *total the block total.
-template <typename T>
-__device__ __forceinline__ T block_excl_scan(T v, T* sh /* >= 17 */, T* total) {
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const T inc = warp_incl_scan(v);
-    if (lane == 63) sh[w] = inc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        T run = T(0);
-        for (int q = 0; q < 16; ++q) {
-            const T t = sh[q];
-            sh[q] = run;
-            run += t;
-        }
-        sh[16] = run;
-    }
-    __syncthreads();
-    const T out = sh[w] + inc - v;
-    *total = sh[16];
-    __syncthreads();
-    return out;
-}
-
-__device__ __forceinline__ int32_t al4(int32_t n) { return (n + 3) & ~3; }
 
 }  // namespace ds
 }  // namespace gs

@@ -472,7 +472,7 @@ __device__ __forceinline__ void finish_union(Ctl* c, const HopBufs& hb, const Un
     int my_keys = 0;
     for (uint32_t i = sa; i < sb; ++i) my_keys += occupied(i);
     int n_src;
-    int rk = block_excl_scan(my_keys, shi, &n_src);
+    int rk = block_excl_scan<16>(my_keys, shi, &n_src);
     if (n_src > nd_next_max) {
         if (tid == 0) c->status |= kStSize;
         return;
@@ -591,7 +591,7 @@ __global__ __launch_bounds__(1024) void ubig_kernel(Ctl* c, HopBufs hb, UnionBuf
             };
             int mine = 0;
             for (uint32_t i = a0; i < a1; ++i) mine += s == 0 ? ub.first_tab[i] != -1 : t16_get(T, i) != 0xFFFFu;
-            int at = block_excl_scan(mine, shi, &n_old);
+            int at = block_excl_scan<16>(mine, shi, &n_old);
             // kGather gathers in flight before the stores (sk may alias sk_prev
             // for the compiler: a plain loop waits out one gather per slot)
             for (uint32_t i0 = a0; i0 < a1; i0 += kGather) {
@@ -686,8 +686,8 @@ __global__ __launch_bounds__(1024) void ublock_kernel(Ctl* c, HopBufs hb, UnionB
         my_fresh += __popcll(ub.fmask[r]);
     }
     int items_tot, fresh_tot;
-    int tp = block_excl_scan(my_items, shi, &items_tot);
-    int f = block_excl_scan(my_fresh, shi, &fresh_tot);
+    int tp = block_excl_scan<16>(my_items, shi, &items_tot);
+    int f = block_excl_scan<16>(my_fresh, shi, &fresh_tot);
     for (int r = ra; r < rb; ++r) {
         ub.tpre[r] = tp;
         ub.ubef[r] = used0 + f;
@@ -827,7 +827,7 @@ __global__ __launch_bounds__(1024) void ublock_kernel(Ctl* c, HopBufs hb, UnionB
                 const int32_t kk = s == 0 ? ub.first_tab[i] : static_cast<int32_t>(T[i]);
                 mine += kk != -1;
             }
-            int at = block_excl_scan(mine, shi, &n_old);
+            int at = block_excl_scan<16>(mine, shi, &n_old);
             for (uint32_t i = a0; i < a1; ++i) {
                 const int32_t kk = s == 0 ? ub.first_tab[i] : static_cast<int32_t>(T[i]);
                 if (kk != -1) {
@@ -936,7 +936,7 @@ __global__ __launch_bounds__(1024) void tscan_kernel(Ctl* c, int hop, int32_t* _
     int mine = 0;
     for (int i = a; i < b; ++i) mine += tcnt[i];
     int tot;
-    int p = block_excl_scan(mine, shi, &tot);
+    int p = block_excl_scan<16>(mine, shi, &tot);
     int32_t* tp = pack + h.off[GS_PK_TPTR];
     for (int i = a; i < b; ++i) {
         const int cc = tcnt[i];

@@ -47,13 +47,14 @@
 
 #include "../host/graph.hpp"
 #include "../host/philox.hpp"
+#include "block_scan.hpp"
+#include "dev_host.hpp"
 #include "fsample.hpp"
 #include "kcommon.hpp"
 
 namespace gs {
 namespace fs {
 
-constexpr int kResSlots = 4;          // runs whose results are kept
 constexpr int kStLimit = 1;           // a frontier or the pack outgrew its bound
 constexpr int kStRange = 2;           // a root id outside the graph
 constexpr int kStEmpty = 4;           // empty neighbourhood with GS_SAMPLE_FAIL_EMPTY
@@ -102,41 +103,6 @@ struct P {
     uint64_t seed, batch_index;
     int32_t gcn;
 };
-
-__device__ __forceinline__ int32_t al4(int32_t n) { return (n + 3) & ~3; }
-
-__device__ __forceinline__ int warp_incl_scan(int v) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o, 64);
-        if ((threadIdx.x & 63) >= o) v += t;
-    }
-    return v;
-}
-
-// Exclusive scan of one value per thread over a block of NW waves; *total the
-// block's sum.  sh: NW + 1 ints.
-template <int NW>
-__device__ __forceinline__ int block_excl_scan(int v, int* sh, int* total) {
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int inc = warp_incl_scan(v);
-    if (lane == 63) sh[w] = inc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = 0;
-        for (int q = 0; q < NW; ++q) {
-            const int t = sh[q];
-            sh[q] = run;
-            run += t;
-        }
-        sh[NW] = run;
-    }
-    __syncthreads();
-    const int out = sh[w] + inc - v;
-    *total = sh[NW];
-    __syncthreads();
-    return out;
-}
 
 // The lanes of this thread's 32-lane group for which pred holds.
 __device__ __forceinline__ uint32_t ballot32(bool pred) {
@@ -571,10 +537,6 @@ __global__ __launch_bounds__(256) void finish_kernel(P p, const int32_t* roots, 
 }
 
 // ------------------------------------------------------------------ handle
-static void hip_ok(hipError_t e, const char* what) {
-    if (e != hipSuccess) gs::fail(GS_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
 struct Fast {
     int32_t n_hops = 0;
     int32_t fanouts[GS_MAX_HOPS] = {};
@@ -586,25 +548,11 @@ struct Fast {
     uint64_t seed = 0;
     P p{};
     int32_t nb_max = 0;  // scan blocks of the largest scan
-    std::vector<void*> owned;
-    FCtl* ctl_host = nullptr;  // pinned mirrors, run i's copied into slot i % kResSlots at its end
-    hipEvent_t run_done[kResSlots] = {};
-    int64_t n_runs = 0;
+    // freed after the destructor's wait: ring first (declared last), then mem
+    DevArena mem{"fast sampler"};
+    RunRing<FCtl> ring;
 
-    template <typename T>
-    T* alloc(int64_t n) {
-        void* q = nullptr;
-        hip_ok(hipMalloc(&q, std::max<int64_t>(n, 1) * sizeof(T)), "hipMalloc(fast sampler)");
-        owned.push_back(q);
-        return static_cast<T*>(q);
-    }
-    ~Fast() {
-        if (n_runs) (void)hipEventSynchronize(run_done[(n_runs - 1) % kResSlots]);
-        for (void* q : owned) (void)hipFree(q);
-        if (ctl_host) (void)hipHostFree(ctl_host);
-        for (hipEvent_t e : run_done)
-            if (e) (void)hipEventDestroy(e);
-    }
+    ~Fast() { (void)ring.wait_last_if_any(); }
 };
 
 Fast* fast_create(const gs_graph* gp, const int32_t* fanouts, int32_t n_hops, int64_t max_roots, int32_t flags) {
@@ -640,38 +588,27 @@ Fast* fast_create(const gs_graph* gp, const int32_t* fanouts, int32_t n_hops, in
             src_max = std::max(src_max, nd);
         }
     }
-    auto up = [&](const void* src, size_t bytes) {
-        void* q = nullptr;
-        hip_ok(hipMalloc(&q, std::max<size_t>(bytes, 1)), "hipMalloc(graph)");
-        f->owned.push_back(q);
-        if (bytes) hip_ok(hipMemcpy(q, src, bytes, hipMemcpyHostToDevice), "hipMemcpy(graph)");
-        return q;
-    };
-    p.row_ptr = static_cast<const int64_t*>(up(g.row_ptr.data(), g.row_ptr.size() * sizeof(int64_t)));
-    p.col = static_cast<const int32_t*>(up(g.col.data(), g.col.size() * sizeof(int32_t)));
+    p.row_ptr = static_cast<const int64_t*>(f->mem.upload(g.row_ptr.data(), g.row_ptr.size() * sizeof(int64_t)));
+    p.col = static_cast<const int32_t*>(f->mem.upload(g.col.data(), g.col.size() * sizeof(int32_t)));
     p.n_nodes = static_cast<int32_t>(g.n_nodes);
     const int64_t words = (g.n_nodes + 31) / 32;
     p.n_words = static_cast<int32_t>((words + kScanBlock - 1) / kScanBlock * kScanBlock);
-    p.bitmap = f->alloc<uint32_t>(p.n_words);
+    p.bitmap = f->mem.alloc<uint32_t>(p.n_words);
     hip_ok(hipMemset(p.bitmap, 0, static_cast<size_t>(p.n_words) * sizeof(uint32_t)), "hipMemset(bitmap)");
-    p.lid = f->alloc<int32_t>(g.n_nodes);
-    for (int32_t j = 0; j < n_hops; ++j) p.F[j] = f->alloc<int32_t>(f->nd_max[j]);
-    p.samp = f->alloc<int32_t>(samp_max);
-    p.cnt = f->alloc<int32_t>(nd_all);
-    p.nbrcnt = f->alloc<int32_t>(nd_all);
-    p.tcnt = f->alloc<int32_t>(src_max);
-    p.traw = f->alloc<int32_t>(traw_max);
+    p.lid = f->mem.alloc<int32_t>(g.n_nodes);
+    for (int32_t j = 0; j < n_hops; ++j) p.F[j] = f->mem.alloc<int32_t>(f->nd_max[j]);
+    p.samp = f->mem.alloc<int32_t>(samp_max);
+    p.cnt = f->mem.alloc<int32_t>(nd_all);
+    p.nbrcnt = f->mem.alloc<int32_t>(nd_all);
+    p.tcnt = f->mem.alloc<int32_t>(src_max);
+    p.traw = f->mem.alloc<int32_t>(traw_max);
     p.longs_cap = static_cast<int32_t>(traw_max / 65 + 1);  // a listed segment holds > 64 of the keys
-    p.longs = f->alloc<int32_t>(p.longs_cap);
+    p.longs = f->mem.alloc<int32_t>(p.longs_cap);
     f->nb_max = static_cast<int32_t>(std::max<int64_t>(p.n_words, std::max(nd_all, src_max) + kScanBlock) / kScanBlock);
-    p.bsum = f->alloc<int32_t>(f->nb_max + 1);
-    p.ctl = f->alloc<FCtl>(1);
+    p.bsum = f->mem.alloc<int32_t>(f->nb_max + 1);
+    p.ctl = f->mem.alloc<FCtl>(1);
     hip_ok(hipMemset(p.ctl, 0, sizeof(FCtl)), "hipMemset");
     p.gcn = (flags & GS_SAMPLE_GCN) ? 1 : 0;
-    hip_ok(hipHostMalloc(reinterpret_cast<void**>(&f->ctl_host), kResSlots * sizeof(FCtl), hipHostMallocDefault),
-           "hipHostMalloc");
-    std::memset(f->ctl_host, 0, kResSlots * sizeof(FCtl));
-    for (hipEvent_t& e : f->run_done) hip_ok(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
     hip_ok(hipDeviceSynchronize(), "hipDeviceSynchronize");
     return f.release();
 }
@@ -685,7 +622,7 @@ int64_t fast_pack_bound(const Fast* f, int64_t n_roots) {
     return gs_sample_pack_bound(f->host_graph, n_roots, f->fanouts, f->n_hops) + n_roots;
 }
 
-int64_t fast_runs(const Fast* f) { return f->n_runs; }
+int64_t fast_runs(const Fast* f) { return f->ring.runs(); }
 
 template <int MODE>
 static void launch_scan(const P& p, int hop, int k, int64_t n_max, hipStream_t st) {
@@ -752,52 +689,17 @@ void fast_run_at(Fast* f, int64_t batch_index, const int32_t* roots, int64_t n_r
     }
     finish_kernel<<<root_blocks, 256, 0, st>>>(p, roots, nr, (f->flags & GS_SAMPLE_FAIL_EMPTY) ? 1 : 0, f->n_hops);
     gs::check_launch("fsample finish_kernel");
-    const int slot = static_cast<int>(f->n_runs % kResSlots);
-    hip_ok(hipMemcpyAsync(f->ctl_host + slot, p.ctl, sizeof(FCtl), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(ctl)");
-    hip_ok(hipEventRecord(f->run_done[slot], st), "hipEventRecord");
-    ++f->n_runs;
+    f->ring.record(p.ctl, st);
 }
 
-bool fast_run_ready(Fast* f, int64_t run) {
-    if (run < 0) run = f->n_runs - 1;
-    if (run < 0 || run < f->n_runs - kResSlots) return true;
-    if (run >= f->n_runs) return false;
-    const hipError_t e = hipEventQuery(f->run_done[run % kResSlots]);
-    if (e == hipErrorNotReady) return false;
-    hip_ok(e, "hipEventQuery(fast sampler run)");
-    return true;
-}
+bool fast_run_ready(Fast* f, int64_t run) { return f->ring.ready(run); }
 
 void fast_result_of(Fast* f, int64_t run, int64_t* hop_sizes, int64_t* offsets, int64_t* used) {
-    if (run < 0) {
-        GS_REQUIRE(f->n_runs > 0, GS_EINVAL, "no run to report");
-        run = f->n_runs - 1;
-    }
-    GS_REQUIRE(run < f->n_runs && run >= f->n_runs - kResSlots, GS_ERANGE,
-               "device sampler: run not issued or no longer kept (the last " + std::to_string(kResSlots) +
-                   " runs are)");
-    const int slot = static_cast<int>(run % kResSlots);
-    hip_ok(hipEventSynchronize(f->run_done[slot]), "hipEventSynchronize");
-    const FCtl& c = f->ctl_host[slot];
+    const FCtl& c = f->ring.wait(run);
     if (c.status & kStRange) gs::fail(GS_ERANGE, "node id out of range");
     if (c.status & kStLimit) gs::fail(GS_ELIMIT, "fast sampler: a frontier or the pack outgrew its bound");
     if (c.status & kStEmpty) gs::fail(GS_EEMPTY, "empty neighbourhood");
-    for (int32_t j = 0; j < GS_MAX_HOPS; ++j) {
-        const bool on = j < f->n_hops;
-        const bool last = j == f->n_hops - 1;
-        if (hop_sizes) {
-            hop_sizes[4 * j] = on ? c.hop[j].n_dst : 0;
-            hop_sizes[4 * j + 1] = on ? c.hop[j].n_pos : 0;
-            hop_sizes[4 * j + 2] = on ? (last ? -1 : c.hop[j].n_src) : 0;
-            hop_sizes[4 * j + 3] = on ? (last ? -1 : c.hop[j].n_nbr) : 0;
-        }
-        if (offsets)
-            for (int fi = 0; fi < GS_PK_NFIELDS; ++fi) {
-                const bool lastf = fi == GS_PK_POS_PTR || fi == GS_PK_POS || fi == GS_PK_DST_IDS;
-                offsets[j * GS_PK_NFIELDS + fi] = on && (last == lastf) ? c.hop[j].off[fi] : -1;
-            }
-    }
-    if (used) *used = c.used;
+    report_layout(c, f->n_hops, hop_sizes, offsets, used);
 }
 
 }  // namespace fs

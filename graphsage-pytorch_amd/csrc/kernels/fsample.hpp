@@ -24,7 +24,7 @@ int64_t fast_runs(const Fast* f);
 // run < 0: the last run.  Waits for that run and reports it as
 // gs_sample_pack_run would (throws its error).
 void fast_result_of(Fast* f, int64_t run, int64_t* hop_sizes, int64_t* offsets, int64_t* used);
-bool fast_run_ready(Fast* f, int64_t run);  // run < 0: the last run
+bool fast_run_ready(Fast* f, int64_t run);  // run number `run` has finished (no wait)
 
 }  // namespace fs
 }  // namespace gs

@@ -210,8 +210,7 @@ int top_fwd_bwd(int agg, int64_t B, int64_t C, const float* Hprev, const int32_t
                 const int32_t* roots, float* aggo, int32_t* argmax, float* E, float* dZ, float* dIn, float* slab,
                 hipStream_t st, const int32_t* tids = nullptr, int tk = 0, LaunchTimer* timer = nullptr);
 
-// dsample.hip: whether the last gs_dsampler_run has completed (no wait).
-bool dsampler_ready(gs_dsampler* ds);
-bool dsampler_run_ready(gs_dsampler* ds, int64_t run);  // run number `run` has finished
+// dsample.hip: whether run number `run` of the handle has finished (no wait).
+bool dsampler_run_ready(gs_dsampler* ds, int64_t run);
 
 }  // namespace gs

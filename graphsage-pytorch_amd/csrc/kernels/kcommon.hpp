@@ -160,6 +160,10 @@ inline void check_launch(const char* what) {
     if (e != hipSuccess) fail(GS_EHIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
+inline void hip_ok(hipError_t e, const char* what) {
+    if (e != hipSuccess) fail(GS_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // In-kernel span of a timed launch (the bench's roofline timers, step_timer.hip): a

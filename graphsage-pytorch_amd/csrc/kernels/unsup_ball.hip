@@ -22,14 +22,11 @@
 
 #include "../host/graph.hpp"
 #include "../host/unsup_dev.hpp"
+#include "dev_host.hpp"
 #include "kcommon.hpp"
 
 namespace gs {
 namespace {
-
-void hip_ok(hipError_t e, const char* what) {
-    if (e != hipSuccess) fail(GS_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-}
 
 __global__ void ball_seed_kernel(const int32_t* __restrict__ roots, int n_roots, int64_t n_nodes,
                                  unsigned long long* __restrict__ S, unsigned long long* __restrict__ E) {
@@ -209,7 +206,7 @@ __global__ __launch_bounds__(64) void far_list_kernel(const int32_t* __restrict_
 struct UnsupDev {
     int64_t n_nodes = 0;
     int n_order = 0, n_chunks = 0;
-    std::vector<void*> owned;
+    DevArena mem{"unsup dev"};
     const int64_t* t_ptr = nullptr;  // transposed CSR (in-neighbours) for the pulls
     const int32_t* t_col = nullptr;
     int32_t* copy_order = nullptr;  // list(set(train).copy())
@@ -231,31 +228,17 @@ struct UnsupDev {
     uint8_t* req_kind = nullptr;
     hipStream_t st = nullptr;
 
-    template <typename T>
-    T* alloc(int64_t n) {
-        void* p = nullptr;
-        hip_ok(hipMalloc(&p, std::max<int64_t>(n, 1) * sizeof(T)), "hipMalloc(unsup dev)");
-        owned.push_back(p);
-        return static_cast<T*>(p);
-    }
     // A grown buffer replaces the old one, which is freed at once: every call
     // ends with a stream synchronise, so no launch still reads it.
     template <typename T>
     void regrow(T*& p, int64_t n) {
-        if (p) {
-            owned.erase(std::remove(owned.begin(), owned.end(), static_cast<void*>(p)), owned.end());
-            hip_ok(hipFree(p), "hipFree(unsup dev)");
-        }
-        p = alloc<T>(n);
+        if (p) mem.release(p);
+        p = mem.alloc<T>(n);
     }
-    void free_all() {
+    ~UnsupDev() {  // `mem` frees the buffers after this body
         if (st) (void)hipStreamSynchronize(st);
-        for (void* p : owned) (void)hipFree(p);
-        owned.clear();
         if (st) (void)hipStreamDestroy(st);
-        st = nullptr;
     }
-    ~UnsupDev() { free_all(); }
 };
 
 // The device half owns a non-blocking stream on the current device: its calls
@@ -269,11 +252,7 @@ UnsupDev* unsup_dev_create(const Graph& g, const std::vector<int32_t>& copy_orde
     d->n_nodes = g.n_nodes;
     d->n_order = static_cast<int>(copy_order.size());
     d->n_chunks = std::max(1, (d->n_order + 63) / 64);
-    auto up = [&](const void* src, size_t bytes) {
-        void* p = d->alloc<uint8_t>(static_cast<int64_t>(bytes));
-        if (bytes) hip_ok(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice), "hipMemcpy(unsup dev)");
-        return p;
-    };
+    auto up = [&](const void* src, size_t bytes) { return d->mem.upload(src, bytes); };
     {  // in-neighbour CSR by a counting sort over col (order within a row is irrelevant to OR)
         const int64_t n = g.n_nodes, m = g.row_ptr[n];
         std::vector<int64_t> tp(n + 1, 0);

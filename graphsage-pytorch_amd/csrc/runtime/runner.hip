@@ -53,10 +53,6 @@ static double secs(Clock::time_point a, Clock::time_point b) {
     return std::chrono::duration<double>(b - a).count();
 }
 
-static void hip_ok(hipError_t e, const char* what) {
-    if (e != hipSuccess) fail(GS_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
 // The runner's events only order work: the host never reads device memory
 // through them (it waits on them before reusing a slot whose device twin a
 // step has read, or a device buffer whose readers have finished), and cross-stream

@@ -252,7 +252,65 @@ def philox4x32(ctr, key):
     return out
 
 
-class DeviceSampler:
+class _DeviceSamplerHandle:
+    """A gs_dsampler handle on one HIP device: what DeviceSampler and
+    FastDeviceSampler share."""
+
+    def __init__(self, graph, fanouts, max_roots, flags, device):
+        self.fanouts = fanouts
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError(f"{type(self).__name__} runs on a HIP device")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            check(lib().gs_dsampler_create(graph._h, ptr(self.fanouts), len(self.fanouts), int(max_roots), flags,
+                                           ctypes.byref(h)))
+        self._h = h
+        self.graph = graph  # keep the host graph alive (pack bounds)
+        self.n_hops = len(self.fanouts)
+
+    def pack_bound(self, n_roots):
+        return int(lib().gs_dsampler_pack_bound(self._h, int(n_roots)))
+
+    def _run(self, enqueue, roots, pack):
+        """Sample one batch with ``enqueue(roots_ptr, n, pack_ptr, cap, stream)``, one of the
+        library's run entry points; returns (pack, hop_sizes[n_hops, 4], offsets[8, 8], used)."""
+        if not isinstance(roots, torch.Tensor):
+            roots = torch.as_tensor(np.asarray(roots, np.int64).astype(np.int32))
+        # device pointers only: a CPU or strided roots tensor would hand the
+        # kernels host memory or the wrong ids
+        roots = roots.to(device=self.device, dtype=torch.int32).contiguous().view(-1)
+        n = int(roots.numel())
+        if pack is None:
+            bound = self.pack_bound(n)
+            if bound < 0:
+                raise ValueError("n_roots out of [1, max_roots]")
+            pack = torch.zeros(bound, dtype=torch.int32, device=self.device)
+        elif not (isinstance(pack, torch.Tensor) and pack.dtype == torch.int32 and pack.is_contiguous()
+                  and pack.device == self.device):
+            raise ValueError(f"pack must be a contiguous int32 tensor on {self.device}")
+        check(enqueue(ptr(roots), n, ptr(pack), int(pack.numel()), _lib.stream_ptr(self.device)))
+        hs = np.zeros(4 * _lib.GS_MAX_HOPS, np.int64)
+        off = np.zeros(_lib.GS_MAX_HOPS * _lib.GS_PK_NFIELDS, np.int64)
+        used = ctypes.c_int64()
+        check(lib().gs_dsampler_result(self._h, ptr(hs), ptr(off), ctypes.byref(used)))
+        return pack, hs.reshape(-1, 4)[:self.n_hops], off.reshape(_lib.GS_MAX_HOPS, _lib.GS_PK_NFIELDS), \
+            int(used.value)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and getattr(_lib, "_lib", None) is not None:  # _lib is None at interpreter exit
+            _lib._lib.gs_dsampler_destroy(h)
+            self._h = None
+
+
+def _sample_flags(gcn, fail_empty):
+    return (_lib.GS_SAMPLE_GCN if gcn else 0) | (_lib.GS_SAMPLE_FAIL_EMPTY if fail_empty else 0)
+
+
+class DeviceSampler(_DeviceSamplerHandle):
     """The hop loop of GraphSage.forward (models.py:246-251 over
     _get_unique_neighs_list, :277-289) on the GPU: a device
     copy of the graph and a device MT19937 stream produce the same int32 pack
@@ -263,21 +321,9 @@ class DeviceSampler:
     (``RNG`` objects or ``random.getstate()``-style (mt, pos) pairs)."""
 
     def __init__(self, graph, fanouts, max_roots, gcn=False, fail_empty=False, device=None):
-        from ._lib import GS_SAMPLE_GCN
-        self.fanouts = np.ascontiguousarray(fanouts, np.int32)
-        flags = (GS_SAMPLE_GCN if gcn else 0) | (4 if fail_empty else 0)
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("DeviceSampler runs on a HIP device")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            check(lib().gs_dsampler_create(graph._h, ptr(self.fanouts), len(self.fanouts), int(max_roots), flags,
-                                           ctypes.byref(h)))
-        self._h = h
-        self.graph = graph  # keep the host graph alive (pack bounds)
-        self.n_hops = len(self.fanouts)
+        # not _fanouts(): the last hop's fanout may be 0 (the whole neighbourhood)
+        super().__init__(graph, np.ascontiguousarray(fanouts, np.int32), max_roots, _sample_flags(gcn, fail_empty),
+                         device)
 
     def set_rng(self, rng):
         mt, pos = rng.getstate() if isinstance(rng, RNG) else rng
@@ -295,38 +341,12 @@ class DeviceSampler:
         check(lib().gs_dsampler_words(self._h, int(n), ptr(out), _lib.stream_ptr(self.device)))
         return out[:int(n)]
 
-    def pack_bound(self, n_roots):
-        return int(lib().gs_dsampler_pack_bound(self._h, int(n_roots)))
-
     def run(self, roots, pack=None):
         """Sample one batch; returns (pack, hop_sizes[n_hops, 4], offsets[8, 8], used)."""
-        if not isinstance(roots, torch.Tensor):
-            roots = torch.as_tensor(np.asarray(roots, np.int64).astype(np.int32))
-        # device pointers only: a CPU or strided roots tensor would hand the
-        # kernels host memory or the wrong ids
-        roots = roots.to(device=self.device, dtype=torch.int32).contiguous().view(-1)
-        n = int(roots.numel())
-        if pack is None:
-            pack = torch.zeros(self.pack_bound(n), dtype=torch.int32, device=self.device)
-        elif not (isinstance(pack, torch.Tensor) and pack.dtype == torch.int32 and pack.is_contiguous()
-                  and pack.device == self.device):
-            raise ValueError(f"pack must be a contiguous int32 tensor on {self.device}")
-        check(lib().gs_dsampler_run(self._h, ptr(roots), n, ptr(pack), int(pack.numel()), _lib.stream_ptr(self.device)))
-        hs = np.zeros(4 * _lib.GS_MAX_HOPS, np.int64)
-        off = np.zeros(_lib.GS_MAX_HOPS * _lib.GS_PK_NFIELDS, np.int64)
-        used = ctypes.c_int64()
-        check(lib().gs_dsampler_result(self._h, ptr(hs), ptr(off), ctypes.byref(used)))
-        return pack, hs.reshape(-1, 4)[:self.n_hops], off.reshape(_lib.GS_MAX_HOPS, _lib.GS_PK_NFIELDS), \
-            int(used.value)
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value and getattr(_lib, "_lib", None) is not None:  # _lib is None at interpreter exit
-            _lib._lib.gs_dsampler_destroy(h)
-            self._h = None
+        return self._run(lambda *a: lib().gs_dsampler_run(self._h, *a), roots, pack)
 
 
-class FastDeviceSampler:
+class FastDeviceSampler(_DeviceSamplerHandle):
     """The counter-based sampler on the GPU (a gs_dsampler created
     with GS_DSAMPLER_FAST): ``run(roots, batch_index)`` writes, in device
     memory, the pack ``fast_sample(graph, seed, batch_index, roots, ...)``
@@ -334,56 +354,14 @@ class FastDeviceSampler:
     and no ``random`` stream."""
 
     def __init__(self, graph, fanouts, max_roots, seed, gcn=False, fail_empty=False, device=None):
-        self.fanouts = _fanouts(fanouts)
-        flags = (_lib.GS_SAMPLE_GCN if gcn else 0) | (_lib.GS_SAMPLE_FAIL_EMPTY if fail_empty else 0)
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("FastDeviceSampler runs on a HIP device")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            check(lib().gs_dsampler_create(graph._h, ptr(self.fanouts), len(self.fanouts), int(max_roots),
-                                           flags | _lib.GS_DSAMPLER_FAST, ctypes.byref(h)))
-        self._h = h
-        self.graph = graph  # keep the host graph alive (pack bounds)
-        self.n_hops = len(self.fanouts)
+        super().__init__(graph, _fanouts(fanouts), max_roots, _sample_flags(gcn, fail_empty) | _lib.GS_DSAMPLER_FAST,
+                         device)
         self.set_seed(seed)
 
     def set_seed(self, seed):
         self.seed = int(seed) & (2 ** 64 - 1)
         check(lib().gs_dsampler_set_seed(self._h, self.seed))
 
-    def pack_bound(self, n_roots):
-        return int(lib().gs_dsampler_pack_bound(self._h, int(n_roots)))
-
     def run(self, roots, batch_index, pack=None):
         """Sample one batch; returns (pack, hop_sizes[n_hops, 4], offsets[8, 8], used)."""
-        if not isinstance(roots, torch.Tensor):
-            roots = torch.as_tensor(np.asarray(roots, np.int64).astype(np.int32))
-        # device pointers only: a CPU or strided roots tensor would hand the
-        # kernels host memory or the wrong ids
-        roots = roots.to(device=self.device, dtype=torch.int32).contiguous().view(-1)
-        n = int(roots.numel())
-        if pack is None:
-            bound = self.pack_bound(n)
-            if bound < 0:
-                raise ValueError("n_roots out of [1, max_roots]")
-            pack = torch.zeros(bound, dtype=torch.int32, device=self.device)
-        elif not (isinstance(pack, torch.Tensor) and pack.dtype == torch.int32 and pack.is_contiguous()
-                  and pack.device == self.device):
-            raise ValueError(f"pack must be a contiguous int32 tensor on {self.device}")
-        check(lib().gs_dsampler_run_at(self._h, int(batch_index), ptr(roots), n, ptr(pack), int(pack.numel()),
-                                       _lib.stream_ptr(self.device)))
-        hs = np.zeros(4 * _lib.GS_MAX_HOPS, np.int64)
-        off = np.zeros(_lib.GS_MAX_HOPS * _lib.GS_PK_NFIELDS, np.int64)
-        used = ctypes.c_int64()
-        check(lib().gs_dsampler_result(self._h, ptr(hs), ptr(off), ctypes.byref(used)))
-        return pack, hs.reshape(-1, 4)[:self.n_hops], off.reshape(_lib.GS_MAX_HOPS, _lib.GS_PK_NFIELDS), \
-            int(used.value)
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value and getattr(_lib, "_lib", None) is not None:  # _lib is None at interpreter exit
-            _lib._lib.gs_dsampler_destroy(h)
-            self._h = None
+        return self._run(lambda *a: lib().gs_dsampler_run_at(self._h, int(batch_index), *a), roots, pack)

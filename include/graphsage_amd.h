@@ -283,7 +283,10 @@ int gs_dsampler_words(gs_dsampler* ds, int64_t n, uint32_t* out, void* stream);
 int64_t gs_dsampler_pack_bound(const gs_dsampler* ds, int64_t n_roots);
 /* Sample one batch (device int32 roots) into a device pack, asynchronously on
  * `stream`; gs_dsampler_result waits for it and reports the layout exactly as
- * gs_sample_pack_run does (hop_sizes, offsets, used), or its error. */
+ * gs_sample_pack_run does (hop_sizes, offsets, used), or its error.
+ * GS_EEMPTY fails that run only (it sampled its whole batch); after another
+ * error of the bit-exact sampler the stream is where the run stopped, and the
+ * later runs report the same error until gs_dsampler_set_rng. */
 int gs_dsampler_run(gs_dsampler* ds, const int32_t* roots, int64_t n_roots, int32_t* pack,
                     int64_t cap, void* stream);
 int gs_dsampler_result(gs_dsampler* ds, int64_t* hop_sizes, int64_t* offsets, int64_t* used);
