@@ -1,11 +1,15 @@
 // Host-side plumbing shared by the handles that own device memory (the two
-// device samplers, dsample.hip and fsample.hip, and UnsupDev, unsup_ball.hip):
-// an owning device arena, the ring of per-run results and the layout report.
+// device samplers, dsample.hip and fsample.hip, UnsupDev, unsup_ball.hip, the
+// trainer, trainer.hpp, and the runner, runner.hip): an owning device arena,
+// the ring of per-run results and the layout report.
 // Included by .hip files only.
 //
 // Destruction: an owner's destructor body waits for its outstanding work and
 // destroys its own streams and events; its DevArena / RunRing members free
-// their memory afterwards, as members are destroyed after the body.
+// their memory afterwards, as members are destroyed after the body.  The
+// trainer has no work of its own to wait for (its launches go to its callers'
+// streams, and hipFree waits for the device): its timers destroy their events
+// as members, before the arena declared ahead of them frees.
 #pragma once
 
 #include <algorithm>
@@ -17,9 +21,11 @@
 
 namespace gs {
 
-// Device allocations freed together.  `label` names the owner in error strings.
+// Device allocations freed together.  `label` names the owner in error strings;
+// a refused allocation fails with `alloc_status` (GS_ENOMEM where the owner's
+// callers expect out-of-memory as such).
 struct DevArena {
-    explicit DevArena(const char* label) : label_(label) {}
+    explicit DevArena(const char* label, int alloc_status = GS_EHIP) : label_(label), alloc_status_(alloc_status) {}
     DevArena(const DevArena&) = delete;
     DevArena& operator=(const DevArena&) = delete;
     ~DevArena() {
@@ -29,7 +35,12 @@ struct DevArena {
     template <typename T>
     T* alloc(int64_t n) {
         void* p = nullptr;
-        hip_ok(hipMalloc(&p, std::max<int64_t>(n, 1) * sizeof(T)), what("hipMalloc").c_str());
+        const hipError_t e = hipMalloc(&p, std::max<int64_t>(n, 1) * sizeof(T));
+        if (e != hipSuccess) {
+            // reported here, once: not again by the next check_launch on this thread
+            (void)hipGetLastError();
+            fail(alloc_status_, what("hipMalloc") + ": " + hipGetErrorString(e));
+        }
         owned_.push_back(p);
         return static_cast<T*>(p);
     }
@@ -48,6 +59,7 @@ struct DevArena {
   private:
     std::string what(const char* call) const { return std::string(call) + "(" + label_ + ")"; }
     const char* label_;
+    const int alloc_status_;
     std::vector<void*> owned_;
 };
 

@@ -164,6 +164,11 @@ inline void hip_ok(hipError_t e, const char* what) {
     if (e != hipSuccess) fail(GS_EHIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
+// The status of one of this library's own C-ABI calls: its error goes on as it was reported.
+inline void ok(int rc) {
+    if (rc != GS_OK) fail(rc, gs_last_error());
+}
+
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // In-kernel span of a timed launch (the bench's roofline timers, step_timer.hip): a

@@ -5,14 +5,12 @@
 // The Python host makes two calls per step (forward_backward, update) and
 // puts the RCCL gradient all-reduce between them.
 #include <algorithm>
+#include <memory>
+#include <utility>
 
 #include "trainer.hpp"
 
 namespace gs {
-
-static inline void ok(int rc) {
-    if (rc != GS_OK) fail(rc, gs_last_error());
-}
 
 // Field f of hop `hop` (1-based) in a packed sample.
 static inline const int32_t* pack_field(const int32_t* pack, const int64_t* offsets, int hop, int f) {
@@ -40,38 +38,36 @@ static void gather1(gs_trainer& T, const int32_t* pack, const int64_t* hop_sizes
 // into padded neighbour ids, then gather rows through them (the timed launch;
 // bitwise the expand-mode result).
 static void gather1_ids(gs_trainer& T, const int32_t* pack, const int64_t* hop_sizes, const int64_t* offsets,
-                        int slot, hipStream_t st) {
+                        GatherSlot& g, hipStream_t st) {
     const gs_trainer_config& c = T.cfg;
     const int L = c.n_layers;
     auto fld = [&](int f) { return pack_field(pack, offsets, L, f); };
     const int64_t n_dst = hop_sizes[4 * (L - 1)];
-    int32_t* ids = T.ids_slot[slot];
     const int64_t n_top = hop_sizes[0];
-    T.top_ready[slot] = T.top_k > 0 && L == 2 && !c.gcn && n_top <= T.top_rows && T.top_slot[slot] &&
-                        hop_sizes[3] <= n_top * T.top_k;  // every root's list fits tk slots
+    g.top_ready = T.top_k > 0 && L == 2 && !c.gcn && n_top <= T.top_rows && g.top &&
+                  hop_sizes[3] <= n_top * T.top_k;  // every root's list fits tk slots
     const int64_t n_rec = hop_sizes[2];  // |L1|: hop 1's sources
-    T.rec_ready[slot] = T.top_ready[slot] && T.rec_slot[slot] && n_rec <= T.rec_rows;
-    if (T.top_ready[slot]) {
+    g.rec_ready = g.top_ready && g.rec && n_rec <= T.rec_rows;
+    if (g.top_ready) {
         auto f1 = [&](int f) { return pack_field(pack, offsets, 1, f); };
-        resolve_top_launch(n_dst, T.k_ids, fld(GS_PK_POS_PTR), fld(GS_PK_POS), c.col, fld(GS_PK_DST_IDS), c.gcn, ids,
-                           n_top, T.top_k, f1(GS_PK_NBR_PTR), f1(GS_PK_NBR), f1(GS_PK_SELF), T.top_slot[slot], st,
-                           T.rec_ready[slot] ? n_rec : 0, f1(GS_PK_TPTR), f1(GS_PK_TIDX), T.rec_slot[slot]);
+        resolve_top_launch(n_dst, T.k_ids, fld(GS_PK_POS_PTR), fld(GS_PK_POS), c.col, fld(GS_PK_DST_IDS), c.gcn, g.ids,
+                           n_top, T.top_k, f1(GS_PK_NBR_PTR), f1(GS_PK_NBR), f1(GS_PK_SELF), g.top, st,
+                           g.rec_ready ? n_rec : 0, f1(GS_PK_TPTR), f1(GS_PK_TIDX), g.rec);
     } else {
-        resolve_ids_launch(n_dst, T.k_ids, fld(GS_PK_POS_PTR), fld(GS_PK_POS), c.col, fld(GS_PK_DST_IDS), c.gcn, ids,
+        resolve_ids_launch(n_dst, T.k_ids, fld(GS_PK_POS_PTR), fld(GS_PK_POS), c.col, fld(GS_PK_DST_IDS), c.gcn, g.ids,
                            st);
     }
     LaunchTimer timed = timed_arm(T, 0);
     if (T.self_rows) {  // [self | agg] rows
-        char* base = static_cast<char*>(T.a1_slot[slot]);
+        char* base = static_cast<char*>(g.a1);
         const int64_t xsz = c.feat_dtype == GS_BF16 ? 2 : 4;
         agg_ids_launch(static_cast<gs_agg>(c.agg), static_cast<gs_dtype>(c.feat_dtype), c.X, c.feat_ld, c.feat_dim,
-                       n_dst, T.k_ids, ids, fld(GS_PK_DST_IDS), c.gcn, base + c.feat_dim * xsz, 2 * c.feat_dim, st,
+                       n_dst, T.k_ids, g.ids, fld(GS_PK_DST_IDS), c.gcn, base + c.feat_dim * xsz, 2 * c.feat_dim, st,
                        base, 2 * c.feat_dim, &timed);
-        T.self_in_slot[slot] = true;
+        g.self_in = true;
     } else {
         agg_ids_launch(static_cast<gs_agg>(c.agg), static_cast<gs_dtype>(c.feat_dtype), c.X, c.feat_ld, c.feat_dim,
-                       n_dst, T.k_ids, ids, fld(GS_PK_DST_IDS), c.gcn, T.a1_slot[slot], c.feat_dim, st, nullptr, 0,
-                       &timed);
+                       n_dst, T.k_ids, g.ids, fld(GS_PK_DST_IDS), c.gcn, g.a1, c.feat_dim, st, nullptr, 0, &timed);
     }
     timed_done(T, 0, timed);
 }
@@ -88,10 +84,10 @@ struct StepPlan {
 };
 
 // The only code that carves the workspace (with ws == nullptr it only sizes).
-// With a1_slot >= 0 the layer-1 aggregate is that gather slot; with embed_out
+// With a gather slot the layer-1 aggregate is that slot's; with embed_out
 // the last layer writes there.
-static StepPlan plan_step(gs_trainer& T, const int64_t* hop_sizes, int64_t B, char* ws, int64_t ws_bytes, int a1_slot,
-                          float* embed_out) {
+static StepPlan plan_step(gs_trainer& T, const int64_t* hop_sizes, int64_t B, char* ws, int64_t ws_bytes,
+                          const GatherSlot* slot, float* embed_out) {
     const gs_trainer_config& c = T.cfg;
     const int L = c.n_layers;
     const int64_t H = c.hidden, F = c.feat_dim;
@@ -102,9 +98,9 @@ static StepPlan plan_step(gs_trainer& T, const int64_t* hop_sizes, int64_t B, ch
         p.rows[l - 1] = hop_sizes[4 * (L - l)];  // hop L - l + 1's destinations
         p.in_dim[l - 1] = l == 1 ? F : H;
         if (l == 1) {
-            if (a1_slot >= 0) {
-                GS_REQUIRE(p.rows[0] <= T.a1_rows && T.a1_slot[a1_slot], GS_EINVAL, "gather slot too small");
-                p.agg[0] = T.a1_slot[a1_slot];
+            if (slot) {
+                GS_REQUIRE(p.rows[0] <= T.a1_rows && slot->a1, GS_EINVAL, "gather slot too small");
+                p.agg[0] = slot->a1;
             } else {
                 p.agg[0] = cv.take<char>(p.rows[0] * F * (c.feat_dtype == GS_BF16 ? 2 : 4));
             }
@@ -154,7 +150,7 @@ struct Step {
     int64_t B;
     float* loss;
     hipStream_t st;
-    int a1_slot;
+    const GatherSlot* slot;  // the gather slot that holds the layer-1 aggregate, or NULL (the step gathers itself)
     const StepPlan p;
     const gs_trainer_config& c = T.cfg;
     const int L = c.n_layers;
@@ -170,10 +166,10 @@ struct Step {
 
     void layer1_operands() {
         in = {c.gcn ? nullptr : c.X, c.feat_ld, fld(L, GS_PK_DST_IDS), p.agg[0], F};
-        if (a1_slot >= 0 && T.self_rows) {
+        if (slot && T.self_rows) {
             in.a1 = static_cast<const char*>(p.agg[0]) + F * (dt == GS_BF16 ? 2 : 4);
             in.lda1 = 2 * F;
-            if (T.self_in_slot[a1_slot] && !c.gcn) {
+            if (slot->self_in && !c.gcn) {
                 in.x1 = p.agg[0];
                 in.ldx1 = 2 * F;
                 in.sidx1 = nullptr;
@@ -279,8 +275,8 @@ struct Step {
             a.argmax = p.am[l - 1];
             a.Hprev = p.h[l - 2];
             a.dH = p.dbuf[flip_f];
-            if (top && l == L && a1_slot >= 0 && T.rec_ready[a1_slot])  // the side stream's records of hop 1's lists
-                a.trec = reinterpret_cast<const int4*>(T.rec_slot[a1_slot]);
+            if (top && l == L && slot && slot->rec_ready)  // the side stream's records of hop 1's lists
+                a.trec = reinterpret_cast<const int4*>(slot->rec);
             flip_f ^= 1;
             fusable = fusable && layer_bwd_fusable(a);
         }
@@ -353,11 +349,11 @@ struct Step {
     // writes the deferred update's speculative W1; else backward_fused.
     void backward_top(LayerBwd& lb2) {
         LaunchTimer timed = timed_arm(T, 3);
-        const bool tids = a1_slot >= 0 && T.top_ready[a1_slot];
+        const bool tids = slot && slot->top_ready;
         const int cls_rows = top_fwd_bwd(c.agg, B, c.n_classes, p.h[0], fld(1, GS_PK_NBR_PTR), fld(1, GS_PK_NBR),
                                          fld(1, GS_PK_SELF), P + T.w_off[1], P + T.cls_w_off, P + T.cls_b_off, c.labels,
                                          roots, static_cast<float*>(p.agg[1]), p.am[1], p.h[1], p.demb, p.dIn, p.cls_ws,
-                                         st, tids ? T.top_slot[a1_slot] : nullptr, tids ? T.top_k : 0, &timed);
+                                         st, tids ? slot->top : nullptr, tids ? T.top_k : 0, &timed);
         timed_done(T, 3, timed);
         lb2.din_ready = true;
         const ClsReduce cr = cls_reduce_role(cls_rows);
@@ -447,8 +443,8 @@ struct Step {
 static int64_t run_step(gs_trainer& T, const int32_t* pack, const int64_t* hop_sizes, const int64_t* offsets,
                         const int32_t* roots, int64_t B, char* ws, int64_t ws_bytes, float* loss, hipStream_t st,
                         int a1_slot = -1, float* embed_out = nullptr) {
-    Step s{T, pack, offsets, roots, B, loss, st, a1_slot,
-           plan_step(T, hop_sizes, B, ws, ws_bytes, a1_slot, embed_out)};
+    const GatherSlot* slot = a1_slot >= 0 ? &T.slot[a1_slot] : nullptr;
+    Step s{T, pack, offsets, roots, B, loss, st, slot, plan_step(T, hop_sizes, B, ws, ws_bytes, slot, embed_out)};
     const StepPlan& p = s.p;
     const int L = s.L;
     T.last_emb = p.h[L - 1];
@@ -458,7 +454,7 @@ static int64_t run_step(gs_trainer& T, const int32_t* pack, const int64_t* hop_s
     s.layer1_operands();
     GS_REQUIRE(!T.defer || !embed_out, GS_EINVAL, "deferred update: unsupported step");
     s.w1_for_forward();
-    if (a1_slot < 0) gather1(T, pack, hop_sizes, offsets, p.agg[0], st);
+    if (!slot) gather1(T, pack, hop_sizes, offsets, p.agg[0], st);
     s.forward_layer1();
     // a 2-layer training step runs layer 2, the loss head and layer 2's dIn in
     // one launch (top.hip) inside backward_top
@@ -509,26 +505,29 @@ void trainer_set_w1_chunk_hook(gs_trainer* t, int chunks, std::function<void(hip
     t->w1_chunk_hook = std::move(hook);
 }
 
+// Every gather slot's buffer `buf` anew, `bytes` bytes each (at least 256), or
+// none with bytes < 0.  The caller zeroes the counts that describe these
+// buffers before the call and sets them after it, so a refused allocation
+// leaves counts that promise nothing, and the next reserve starts over.
+template <class P>
+static void regrow_slots(gs_trainer* t, P GatherSlot::*buf, int64_t bytes) {
+    for (GatherSlot& s : t->slot) {
+        if (s.*buf) t->mem.release(std::exchange(s.*buf, nullptr));
+        if (bytes >= 0) s.*buf =static_cast<P>(static_cast<void*>(t->mem.alloc<char>(std::max<int64_t>(bytes, 256))));
+    }
+}
+
 void trainer_reserve_top(gs_trainer* t, int64_t B, int32_t tk) {
     if (t->cfg.n_layers != 2 || t->cfg.gcn || tk < 1 || tk > 31 || B < 1) return;
     if (B <= t->top_rows && tk == t->top_k) return;
-    for (int32_t*& p : t->top_slot) {
-        if (p) GS_REQUIRE(hipFree(p) == hipSuccess, GS_EHIP, "hipFree");
-        p = nullptr;
-        GS_REQUIRE(hipMalloc(&p, std::max<int64_t>(B * (tk + 1) * 4, 256)) == hipSuccess, GS_ENOMEM,
-                   "hipMalloc(top records)");
-    }
-    for (bool& r : t->top_ready) r = false;
+    t->top_rows = t->rec_rows = 0;
+    t->top_k = 0;
+    for (GatherSlot& s : t->slot) s.top_ready = s.rec_ready = false;
+    regrow_slots(t, &GatherSlot::top, B * (tk + 1) * 4);
+    // the backward's records for up to a1_rows layer-1 rows (gs_trainer_gather_reserve first)
+    regrow_slots(t, &GatherSlot::rec, t->a1_rows * 8 * 4);
     t->top_rows = B;
     t->top_k = tk;
-    // the backward's records for up to a1_rows layer-1 rows (gs_trainer_gather_reserve first)
-    for (int32_t*& p : t->rec_slot) {
-        if (p) GS_REQUIRE(hipFree(p) == hipSuccess, GS_EHIP, "hipFree");
-        p = nullptr;
-        GS_REQUIRE(hipMalloc(&p, std::max<int64_t>(t->a1_rows * 8 * 4, 256)) == hipSuccess, GS_ENOMEM,
-                   "hipMalloc(backward records)");
-    }
-    for (bool& r : t->rec_ready) r = false;
     t->rec_rows = t->a1_rows;
 }
 
@@ -549,7 +548,7 @@ int gs_trainer_create(const gs_trainer_config* cfg, gs_trainer** out) {
     GS_REQUIRE(cfg->n_classes >= 1 && cfg->feat_dim >= 1 && cfg->feat_ld >= cfg->feat_dim, GS_EINVAL, "bad dims");
     GS_REQUIRE(cfg->X && cfg->col && cfg->labels && cfg->params && cfg->grads, GS_EINVAL,
                "NULL device pointer");
-    auto* T = new gs_trainer();
+    std::unique_ptr<gs_trainer> T(new gs_trainer());
     T->cfg = *cfg;
     int64_t at = 0;
     for (int l = 1; l <= cfg->n_layers; ++l) {
@@ -569,17 +568,10 @@ int gs_trainer_create(const gs_trainer_config* cfg, gs_trainer** out) {
         for (int l = 1; l <= cfg->n_layers; ++l) np += gs::sum_slabs_grid(cfg->hidden * T->w_cols[l - 1]);
         np = std::max<int64_t>({np, gs::cls_reduce_grid(cfg->n_classes, cfg->hidden), 64});
         T->pstride = static_cast<int>((np + 63) / 64 * 64);
-        if (hipMalloc(&T->norm_part, 2 * T->pstride * sizeof(float)) != hipSuccess) {
-            delete T;
-            gs::fail(GS_ENOMEM, "hipMalloc(norm partials)");
-        }
-        if (cfg->feat_dtype == GS_BF16 &&
-            hipMalloc(&T->w1_lp, T->w_rows[0] * T->w_cols[0] * sizeof(uint16_t)) != hipSuccess) {
-            delete T;
-            gs::fail(GS_ENOMEM, "hipMalloc(bf16 W1)");
-        }
+        T->norm_part = T->mem.alloc<float>(2 * T->pstride);
+        if (cfg->feat_dtype == GS_BF16) T->w1_lp = T->mem.alloc<uint16_t>(T->w_rows[0] * T->w_cols[0]);
     }
-    *out = T;
+    *out = T.release();
     GS_API_END
 }
 
@@ -645,27 +637,16 @@ int gs_trainer_gather_reserve(gs_trainer* t, int64_t max_rows, int32_t max_fanou
     const bool self_rows = t->want_self_rows && !t->cfg.gcn && t->cfg.n_layers >= 1;
     if (max_rows <= t->a1_rows && max_fanout <= t->k_ids && self_rows == t->self_rows) return GS_OK;
     max_rows = std::max(max_rows, t->a1_rows);
-    t->self_rows = self_rows;
-    for (bool& b : t->self_in_slot) b = false;
-    const int64_t bytes = max_rows * t->cfg.feat_dim * (self_rows ? 2 : 1) * (t->cfg.feat_dtype == GS_BF16 ? 2 : 4);
-    for (void*& p : t->a1_slot) {
-        if (p) GS_REQUIRE(hipFree(p) == hipSuccess, GS_EHIP, "hipFree");
-        p = nullptr;
-        GS_REQUIRE(hipMalloc(&p, std::max<int64_t>(bytes, 256)) == hipSuccess, GS_ENOMEM, "hipMalloc(gather slot)");
-    }
-    for (int32_t*& p : t->ids_slot) {
-        if (p) GS_REQUIRE(hipFree(p) == hipSuccess, GS_EHIP, "hipFree");
-        p = nullptr;
-    }
+    GS_REQUIRE(max_rows * max_fanout < (int64_t(1) << 31), GS_EINVAL, "gather slot too large for int32 ids");
+    t->a1_rows = 0;
     t->k_ids = 0;
-    if (max_fanout > 0) {
-        GS_REQUIRE(max_rows * max_fanout < (int64_t(1) << 31), GS_EINVAL, "gather slot too large for int32 ids");
-        for (int32_t*& p : t->ids_slot)
-            GS_REQUIRE(hipMalloc(&p, std::max<int64_t>(max_rows * max_fanout * 4, 256)) == hipSuccess, GS_ENOMEM,
-                       "hipMalloc(gather ids)");
-        t->k_ids = max_fanout;
-    }
+    t->self_rows = self_rows;
+    for (gs::GatherSlot& s : t->slot) s.self_in = false;
+    gs::regrow_slots(t, &gs::GatherSlot::a1,
+                     max_rows * t->cfg.feat_dim * (self_rows ? 2 : 1) * (t->cfg.feat_dtype == GS_BF16 ? 2 : 4));
+    gs::regrow_slots(t, &gs::GatherSlot::ids, max_fanout > 0 ? max_rows * max_fanout * 4 : -1);
     t->a1_rows = max_rows;
+    t->k_ids = max_fanout;
     GS_API_END
 }
 
@@ -675,18 +656,18 @@ int gs_trainer_gather(gs_trainer* t, const int32_t* pack, const int64_t* hop_siz
     GS_REQUIRE(t && pack && hop_sizes && offsets && slot >= 0 && slot < gs_trainer::kSlots, GS_EINVAL,
                "bad arguments");
     const int L = t->cfg.n_layers;
-    GS_REQUIRE(hop_sizes[4 * (L - 1)] <= t->a1_rows && t->a1_slot[slot], GS_EINVAL,
+    gs::GatherSlot& g = t->slot[slot];
+    GS_REQUIRE(hop_sizes[4 * (L - 1)] <= t->a1_rows && g.a1, GS_EINVAL,
                "gather slot too small (gs_trainer_gather_reserve)");
     const int64_t n_dst = hop_sizes[4 * (L - 1)], n_pos = hop_sizes[4 * (L - 1) + 1];
     if (t->k_ids > 0 && n_pos <= n_dst * t->k_ids) {  // every neighbourhood fits k_ids slots
-        gs::gather1_ids(*t, pack, hop_sizes, offsets, slot, gs::as_stream(stream));
+        gs::gather1_ids(*t, pack, hop_sizes, offsets, g, gs::as_stream(stream));
     } else if (t->self_rows) {  // the agg half only: the GEMMs gather the self rows themselves
         const int64_t F = t->cfg.feat_dim, xsz = t->cfg.feat_dtype == GS_BF16 ? 2 : 4;
-        gs::gather1(*t, pack, hop_sizes, offsets, static_cast<char*>(t->a1_slot[slot]) + F * xsz,
-                    gs::as_stream(stream), 2 * F);
-        t->self_in_slot[slot] = false;
+        gs::gather1(*t, pack, hop_sizes, offsets, static_cast<char*>(g.a1) + F * xsz, gs::as_stream(stream), 2 * F);
+        g.self_in = false;
     } else {
-        gs::gather1(*t, pack, hop_sizes, offsets, t->a1_slot[slot], gs::as_stream(stream));
+        gs::gather1(*t, pack, hop_sizes, offsets, g.a1, gs::as_stream(stream));
     }
     GS_API_END
 }

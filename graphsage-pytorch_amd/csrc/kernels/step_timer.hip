@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <utility>
 
 #include "trainer.hpp"
 
@@ -46,6 +47,36 @@ void timed_done(gs_trainer& T, int site, const LaunchTimer& lt) {
 
 }  // namespace gs
 
+void gs_trainer::Timer::drop_events() {
+    for (auto* evs : {&ev0, &ev1}) {
+        for (hipEvent_t e : *evs)
+            if (e) (void)hipEventDestroy(e);
+        evs->clear();
+    }
+}
+
+void gs_trainer::Timer::reset(gs::DevArena& mem, int64_t capacity, bool with_stamps) {
+    drop_events();
+    n = 0;  // nothing is timed or read back until the new entries are complete
+    if (st0) mem.release(std::exchange(st0, nullptr));
+    st1 = nullptr;
+    stamped.assign(capacity, 0);
+    if (with_stamps && capacity > 0) {
+        const int64_t words = capacity * gs::kStampBlocks;
+        st0 = mem.alloc<unsigned long long>(2 * words);
+        st1 = st0 + words;
+        gs::hip_ok(hipMemset(st0, 0, 2 * words * sizeof(unsigned long long)), "hipMemset(timer stamps)");
+    }
+    ev0.assign(capacity, nullptr);
+    ev1.assign(capacity, nullptr);
+    for (int64_t i = 0; i < capacity; ++i) {
+        gs::hip_ok(hipEventCreateWithFlags(&ev0[i], gs::timer_event_flags()), "hipEventCreate");
+        gs::hip_ok(hipEventCreateWithFlags(&ev1[i], gs::timer_event_flags()), "hipEventCreate");
+    }
+    calls = 0;
+    kernel.clear();
+}
+
 extern "C" {
 
 int gs_trainer_time_kernels(gs_trainer* t, int32_t site_mask, int64_t capacity) {
@@ -56,31 +87,9 @@ int gs_trainer_time_kernels_every(gs_trainer* t, int32_t site_mask, int64_t capa
     GS_API_BEGIN
     GS_REQUIRE(t && capacity >= 0 && every >= 1, GS_EINVAL, "bad arguments");
     for (int s = 0; s < gs_trainer::kSites; ++s) {
-        auto& tm = t->timer[s];
-        for (auto e : tm.ev0) (void)hipEventDestroy(e);
-        for (auto e : tm.ev1) (void)hipEventDestroy(e);
-        const int64_t cap = (site_mask >> s) & 1 ? capacity : 0;
-        tm.ev0.assign(cap, nullptr);
-        tm.ev1.assign(cap, nullptr);
-        if (tm.st0) (void)hipFree(tm.st0);
-        tm.st0 = tm.st1 = nullptr;
-        tm.stamped.assign(cap, 0);
-        if (s >= 1 && cap > 0) {  // span stamps (forward, dW, top, slab sum)
-            const int64_t words = cap * gs::kStampBlocks;
-            GS_REQUIRE(hipMalloc(&tm.st0, 2 * words * sizeof(unsigned long long)) == hipSuccess, GS_ENOMEM,
-                       "hipMalloc(timer stamps)");
-            tm.st1 = tm.st0 + words;
-            GS_REQUIRE(hipMemset(tm.st0, 0, 2 * words * sizeof(unsigned long long)) == hipSuccess, GS_EHIP,
-                       "hipMemset(timer stamps)");
-        }
-        for (int64_t i = 0; i < cap; ++i)
-            GS_REQUIRE(hipEventCreateWithFlags(&tm.ev0[i], gs::timer_event_flags()) == hipSuccess &&
-                           hipEventCreateWithFlags(&tm.ev1[i], gs::timer_event_flags()) == hipSuccess,
-                       GS_EHIP, "hipEventCreate");
-        tm.n = 0;
-        tm.every = every;
-        tm.calls = 0;
-        tm.kernel.clear();
+        // span stamps for the sites >= 1 (forward, dW, top, slab sum)
+        t->timer[s].reset(t->mem, (site_mask >> s) & 1 ? capacity : 0, s >= 1);
+        t->timer[s].every = every;
     }
     GS_API_END
 }

@@ -87,17 +87,15 @@ bool trainer_defer_update(gs_trainer* t, bool on, hipStream_t st, bool comm) {
     // operands and applies the update on its own where they do not)
     const int64_t epv = c.feat_dtype == GS_F32 ? 4 : 8;
     // (and only SGD is speculated on: sgd_elem in the slab sum, FwdSpec, sumsq_spec, spec_finalize)
-    const bool ok = t->opt.kind == GS_OPT_SGD && t->opt_defer &&
+    const bool can = t->opt.kind == GS_OPT_SGD && t->opt_defer &&
                     (c.feat_dtype == GS_F32 || (c.feat_dtype == GS_BF16 && t->w1_lp)) &&
                     t->fuse_bwd && t->use_top && c.n_layers == 2 && !c.gcn &&
                     (comm || (!t->upper_hook && !t->w1_chunk_hook)) && n1 % 4 == 0 &&
                     c.feat_dim % epv == 0 && c.feat_ld % epv == 0 && aligned16(c.X) &&
                     t->cls_w_off % 4 == 0 && t->total % 4 == 0 && aligned16(c.params) && aligned16(c.grads);
-    if (!ok) return false;
-    if (!t->w1_alt)
-        GS_REQUIRE(hipMalloc(&t->w1_alt, n1 * sizeof(float)) == hipSuccess, GS_ENOMEM, "hipMalloc(W1 buffer)");
-    if (c.feat_dtype == GS_BF16 && !t->w1_lp_alt)
-        GS_REQUIRE(hipMalloc(&t->w1_lp_alt, n1 * sizeof(uint16_t)) == hipSuccess, GS_ENOMEM, "hipMalloc(bf16 W1)");
+    if (!can) return false;
+    if (!t->w1_alt) t->w1_alt = t->mem.alloc<float>(n1);
+    if (c.feat_dtype == GS_BF16 && !t->w1_lp_alt) t->w1_lp_alt = t->mem.alloc<uint16_t>(n1);
     t->lp_valid = false;  // the first forward casts W1 into lp_buf(0)
     t->defer = true;
     t->defer_comm = comm;
@@ -196,9 +194,9 @@ int gs_trainer_defer(gs_trainer* t, int32_t on, int32_t* active, void* stream) {
     if (on) {
         GS_REQUIRE(!t->defer && !t->pending, GS_EINVAL, "gs_trainer_defer: already deferring");
         gs::trainer_keep_lowp(t, true);  // the bf16 W1 follows every update, as in a runner loop
-        const bool ok = gs::trainer_defer_update(t, true, st, true);
-        if (!ok) gs::trainer_keep_lowp(t, false);
-        if (active) *active = ok ? 1 : 0;
+        const bool deferring = gs::trainer_defer_update(t, true, st, true);
+        if (!deferring) gs::trainer_keep_lowp(t, false);
+        if (active) *active = deferring ? 1 : 0;
     } else {
         if (t->defer) gs::trainer_defer_update(t, false, st);
         gs::trainer_keep_lowp(t, false);

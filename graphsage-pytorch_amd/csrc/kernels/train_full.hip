@@ -146,10 +146,6 @@ __global__ __launch_bounds__(256) void head_combine_kernel(float* __restrict__ D
     reinterpret_cast<float4*>(D)[static_cast<int64_t>(r) * q + c] = g;
 }
 
-void ok(int rc) {
-    if (rc != GS_OK) fail(rc, gs_last_error());
-}
-
 // The caller's buffer of the unsupervised head: the loss kernels' per-pair state, dE of the pair loss and the
 // constant 1.0 that gs_unsup_loss_bwd reads as dloss.
 struct UnsupLayout {

@@ -5,10 +5,14 @@
 #include <string>
 #include <vector>
 
+#include "dev_host.hpp"
 #include "internal.hpp"
 
 struct gs_trainer {
     gs_trainer_config cfg;
+    // every device buffer of the handle; declared ahead of the timers, so
+    // freed after they have destroyed their events (dev_host.hpp)
+    gs::DevArena mem{"trainer", GS_ENOMEM};
     std::vector<int64_t> w_off;  // element offset of each parameter in the flat buffer
     std::vector<int64_t> w_rows, w_cols;
     int64_t cls_w_off = 0, cls_b_off = 0, total = 0;
@@ -27,33 +31,46 @@ struct gs_trainer {
         unsigned long long* st0 = nullptr;  // device: per entry, kStampBlocks workgroup starts (100 MHz ticks)
         unsigned long long* st1 = nullptr;  // device: per entry, the workgroup ends
         std::vector<char> stamped;
+        // Room for `capacity` timed launches from now on (0: the site is off),
+        // with span stamps from `mem` when asked; what the site held goes first.
+        void reset(gs::DevArena& mem, int64_t capacity, bool with_stamps);
+        Timer() = default;
+        Timer(const Timer&) = delete;
+        Timer& operator=(const Timer&) = delete;
+        ~Timer() { drop_events(); }  // (the stamps are the arena's)
+
+      private:
+        void drop_events();
     } timer[kSites];
-    // layer-1 aggregate slots for gathers issued ahead of their step
-    // (gs_trainer_gather), so the next batch's gather overlaps this backward
+    // One layer-1 aggregate slot for a gather issued ahead of its step
+    // (gs_trainer_gather), so the next batch's gather overlaps this backward,
+    // and what is resolved on the side stream with that gather.
+    struct GatherSlot {
+        // a1_rows rows: the aggregate, or [self | agg] rows of 2F (self_rows below)
+        void* a1 = nullptr;
+        bool self_in = false;  // the self half was written
+        // the layer-1 neighbour ids resolved ahead of the gather (k_ids slots
+        // per destination), when reserved with a fanout
+        int32_t* ids = nullptr;
+        // padded hop-1 records for the fused top launch (trainer_reserve_top: top_rows roots, top_k each)
+        int32_t* top = nullptr;
+        bool top_ready = false;
+        // the layer-2 backward's records of the transposed hop-1 lists (8 ints
+        // per layer-1 row, rec_rows rows; written with the top records)
+        int32_t* rec = nullptr;
+        bool rec_ready = false;
+    };
     static constexpr int kSlots = 3;
-    void* a1_slot[kSlots] = {};
-    int64_t a1_rows = 0;
-    // Each gather slot is [self | agg] rows of 2F (option GS_TOPT_SELF_ROWS,
-    // default on; applied at gs_trainer_gather_reserve): the side-stream gather
-    // also copies the layer-1 rows' own features, so the layer-1 forward and dW
-    // read one dense block (no self-index round).  self_in_slot: the slot's self
-    // half was written.
+    GatherSlot slot[kSlots];
+    // What the slots' buffers were reserved for; 0 from a reserve's first free
+    // to its last allocation, so also after a refused one.
+    int64_t a1_rows = 0, top_rows = 0, rec_rows = 0;
+    int k_ids = 0, top_k = 0;
+    // [self | agg] slots (option GS_TOPT_SELF_ROWS, default on; applied at
+    // gs_trainer_gather_reserve): the side-stream gather also copies the
+    // layer-1 rows' own features, so the layer-1 forward and dW read one dense
+    // block (no self-index round).
     bool self_rows = false;
-    bool self_in_slot[kSlots] = {};
-    // per slot, the layer-1 neighbour ids resolved ahead of the gather
-    // (k_ids slots per destination), when reserved with a fanout
-    int32_t* ids_slot[kSlots] = {};
-    int k_ids = 0;
-    // padded hop-1 records for the fused top launch, per gather slot (trainer_reserve_top)
-    int32_t* top_slot[kSlots] = {};
-    bool top_ready[kSlots] = {};
-    int64_t top_rows = 0;
-    int top_k = 0;
-    // per gather slot, the layer-2 backward's records of the transposed hop-1
-    // lists (8 ints per layer-1 row, rec_rows rows; written with the top records)
-    int32_t* rec_slot[kSlots] = {};
-    int64_t rec_rows = 0;
-    bool rec_ready[kSlots] = {};
     // clip-norm partials produced by the fused backward's reduce launches
     // (group 0: the sage weights' slab sums, group 1: the classifier reduce),
     // consumed by gs_trainer_update_local when no all-reduce came between
@@ -123,29 +140,11 @@ struct gs_trainer {
         done = {};
         return d;
     }
-    ~gs_trainer() {
-        if (w1_alt) (void)hipFree(w1_alt);
-        if (w1_lp_alt) (void)hipFree(w1_lp_alt);
-        if (norm_part) (void)hipFree(norm_part);
-        if (w1_lp) (void)hipFree(w1_lp);
-        for (auto& tm : timer) {
-            for (auto e : tm.ev0) (void)hipEventDestroy(e);
-            for (auto e : tm.ev1) (void)hipEventDestroy(e);
-        }
-        for (void* p : a1_slot)
-            if (p) (void)hipFree(p);
-        for (int32_t* p : ids_slot)
-            if (p) (void)hipFree(p);
-        for (int32_t* p : top_slot)
-            if (p) (void)hipFree(p);
-        for (int32_t* p : rec_slot)
-            if (p) (void)hipFree(p);
-        for (auto& tm : timer)
-            if (tm.st0) (void)hipFree(tm.st0);
-    }
 };
 
 namespace gs {
+
+using GatherSlot = gs_trainer::GatherSlot;
 
 // Bump allocator over the workspace (256-byte aligned carves).
 struct Carve {

@@ -41,8 +41,10 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
+#include "../kernels/dev_host.hpp"
 #include "../kernels/internal.hpp"
 
 namespace gs {
@@ -92,16 +94,19 @@ struct SamplerStream {
     std::thread th;
 };
 
-}  // namespace gs
-
-namespace gs {
 struct Inflight {
     int stream = -1, slot = -1;
 };
+
 }  // namespace gs
 
 struct gs_runner {
     gs_runner_config cfg{};
+    // every device buffer of the handle: the step workspace, the clip
+    // workspace, the pack slots' device twins and the device sampler's roots
+    // and pack ring.  A member, so it frees after ~gs_runner's body has drained
+    // every stream that reads them.
+    gs::DevArena mem{"runner"};
     std::vector<int32_t> fanouts;
     std::vector<int64_t> roots;  // n_batches x batch
     int64_t cap = 0;             // int32 words per pack slot (pack bound + roots)
@@ -125,7 +130,8 @@ struct gs_runner {
     // trainer took the one-piece path, so the runner reduces W1 itself)
     hipEvent_t w1_ready = nullptr;
     int w1_issued = 0;
-    // Ring of 3 per batch in flight (b % 3): trainer gather slot, events.
+    // Ring of 3 per batch in flight: batch b has entry ring[b % 3] and the
+    // trainer's gather slot of the same index.
     // The side stream gathers batch b's layer 1 (reads only X and the pack's
     // device twin, complete before its slot was offered) while the main stream runs
     // batch b-1.  No stream ever waits on another's event (a cross-queue wait
@@ -133,26 +139,31 @@ struct gs_runner {
     // three batches back released the ring entry, and that the gather of the
     // batch it is about to issue has completed.
     static constexpr int kDev = 3;
+    struct RingEntry {
+        hipEvent_t done = nullptr;      // main: the step of the batch in this entry finished
+        hipEvent_t gathered = nullptr;  // side: the gather of the batch in this entry
+        bool busy = false;              // `done` is recorded for `batch`
+        int64_t batch = -1;             // the batch whose step last used the entry
+        int64_t flag_step = -1;         // batch whose SGD signals the entry free (-1: none pending)
+        gs::Inflight inflight;          // where that batch's pack is
+    };
+    RingEntry ring[kDev];
     // Host sampler: the packs reach the device from the sampler threads, one
     // hipMemcpyAsync per batch on this stream (the copy engine), each waited
     // for by its thread (hipStreamSynchronize: a later thread's copy on the
     // same stream may be waited for too, a few microseconds).
     hipStream_t copy_stream = nullptr;
-    hipEvent_t dev_done[kDev] = {};        // main: step of the batch in entry k finished
-    bool dev_busy[kDev] = {};              // dev_done[k] is recorded for entry_batch[k]
-    int64_t entry_batch[kDev] = {-1, -1, -1};  // the batch whose step last used entry k
     // every step <= done_upto has finished reading its ring entry and its pack
     // (steps finish in order on one stream, so one mark serves all of them)
     int64_t done_upto = -1;
     // Step completion without an event between steps: the step's SGD launch
     // (with a deferred update: its last slab sum) stores its batch index into done_host (fine-grained pinned memory) when
     // it starts, i.e. once every launch that reads the step's ring entry has
-    // completed (stream order); the host polls it.  dev_done events remain for
+    // completed (stream order); the host polls it.  The entries' done events remain for
     // the last step of each gs_runner_run call (teardown) and for inference.
     bool use_flag = false;
     int64_t* done_host = nullptr;          // hipHostMalloc, coherent
     int64_t* done_dev = nullptr;
-    int64_t flag_step[kDev] = {-1, -1, -1};  // batch whose SGD signals entry k free (-1: none pending)
     void wait_flag(int64_t want) {
         const auto t0 = std::chrono::steady_clock::now();
         for (uint64_t spin = 0; __atomic_load_n(done_host, __ATOMIC_ACQUIRE) < want; ++spin) {
@@ -170,13 +181,13 @@ struct gs_runner {
         }
         done_upto = std::max(done_upto, want);
     }
-    void wait_entry(int k) {
-        if (flag_step[k] >= 0) {
-            wait_flag(flag_step[k]);
-            flag_step[k] = -1;
+    void wait_entry(RingEntry& e) {
+        if (e.flag_step >= 0) {
+            wait_flag(e.flag_step);
+            e.flag_step = -1;
         }
-        if (dev_busy[k]) gs::hip_ok(hipEventSynchronize(dev_done[k]), "hipEventSynchronize");
-        done_upto = std::max(done_upto, entry_batch[k]);
+        if (e.busy) gs::hip_ok(hipEventSynchronize(e.done), "hipEventSynchronize");
+        done_upto = std::max(done_upto, e.batch);
     }
     // Has step b finished reading its ring entry and its pack?  `block`: wait for it.
     bool step_done(int64_t b, bool block) {
@@ -188,23 +199,21 @@ struct gs_runner {
                 return true;
             }
         }
-        const int k = static_cast<int>(b % kDev);
-        if (dev_busy[k] && entry_batch[k] >= b) {
-            const hipError_t e = block ? hipEventSynchronize(dev_done[k]) : hipEventQuery(dev_done[k]);
-            if (e == hipErrorNotReady) return false;
-            gs::hip_ok(e, "step event");
-            done_upto = std::max(done_upto, entry_batch[k]);
+        const RingEntry& e = ring[b % kDev];
+        if (e.busy && e.batch >= b) {
+            const hipError_t err = block ? hipEventSynchronize(e.done) : hipEventQuery(e.done);
+            if (err == hipErrorNotReady) return false;
+            gs::hip_ok(err, "step event");
+            done_upto = std::max(done_upto, e.batch);
             return true;
         }
         if (!block) return false;
         // no event behind this step: its SGD launch signals through the flag
-        GS_REQUIRE(use_flag && flag_step[k] >= b, GS_EINVAL, "runner: a consumed slot's step signals nowhere");
+        GS_REQUIRE(use_flag && e.flag_step >= b, GS_EINVAL, "runner: a consumed slot's step signals nowhere");
         wait_flag(b);
         return true;
     }
-    hipEvent_t gathered[kDev] = {};        // side: gather of the batch in entry k
     hipStream_t side = nullptr;
-    gs::Inflight inflight[kDev];
     int64_t issued = 0;                    // batches whose gather is issued
     void* ws = nullptr;
     int64_t ws_bytes = 0;
@@ -223,12 +232,15 @@ struct gs_runner {
     struct DevStream {
         gs_dsampler* ds = nullptr;
         hipStream_t st = nullptr;
-        // queued runs, oldest first: batch, sampler run number, events around
-        // the run (its device time), already counted in `sampled`
+        // queued runs, oldest first: q[0 .. nq).  Every element keeps its two
+        // events for the runner's life, whether queued or not.
+        struct Queued {
+            int64_t batch = 0, run = 0;          // the batch and its sampler run number
+            hipEvent_t t0 = nullptr, t1 = nullptr;  // around the run (its device time)
+            bool counted = false;                // already counted in `sampled`
+        };
         int nq = 0;
-        int64_t qb[kDevDepthMax] = {}, qrun[kDevDepthMax] = {};
-        hipEvent_t t0[kDevDepthMax] = {}, t1[kDevDepthMax] = {};
-        bool counted[kDevDepthMax] = {};
+        Queued q[kDevDepthMax];
         int64_t next = 0;                       // next batch to enqueue (w, w + S, ...)
     };
     int dev_depth = kDevDepthMax;
@@ -240,7 +252,7 @@ struct gs_runner {
     };
     bool devmode = false;
     bool fastmode = false;  // devmode with the counter-based sampler (cfg.device_sampler == 2): no rng streams
-    // guards dstreams' queues (nq, qb, next, counted): gs_runner_release and
+    // guards dstreams' queues (nq, q, next): gs_runner_release and
     // gs_runner_progress may be called from another thread than gs_runner_run
     std::recursive_mutex dev_mu;
     std::vector<DevStream> dstreams;
@@ -382,19 +394,16 @@ void gs_runner::dev_enqueue(int w) {
     while (d.nq < dev_depth) {
         const int64_t b = d.next;
         if (b >= n_units || b >= release_mark.load()) return;
-        const int q = d.nq;
-        hip_ok(hipEventRecord(d.t0[q], d.st), "hipEventRecord");
+        DevStream::Queued& q = d.q[d.nq];
+        hip_ok(hipEventRecord(q.t0, d.st), "hipEventRecord");
         // counter-based sampler: batch b under index b, whichever stream takes it
-        const int rc = fastmode ? gs_dsampler_run_at(d.ds, b, roots_dev + b * cfg.batch, cfg.batch, dpack[b % n_dpack],
-                                                     dcap, d.st)
-                                : gs_dsampler_run(d.ds, roots_dev + b * cfg.batch, cfg.batch, dpack[b % n_dpack], dcap,
-                                                  d.st);
-        if (rc != GS_OK) fail(rc, gs_last_error());
-        hip_ok(hipEventRecord(d.t1[q], d.st), "hipEventRecord");
-        d.qb[q] = b;
-        d.qrun[q] = gs_dsampler_runs(d.ds) - 1;
-        d.counted[q] = false;
-        d.nq = q + 1;
+        ok(fastmode ? gs_dsampler_run_at(d.ds, b, roots_dev + b * cfg.batch, cfg.batch, dpack[b % n_dpack], dcap, d.st)
+                    : gs_dsampler_run(d.ds, roots_dev + b * cfg.batch, cfg.batch, dpack[b % n_dpack], dcap, d.st));
+        hip_ok(hipEventRecord(q.t1, d.st), "hipEventRecord");
+        q.batch = b;
+        q.run = gs_dsampler_runs(d.ds) - 1;
+        q.counted = false;
+        ++d.nq;
         d.next = b + cfg.n_streams;
     }
 }
@@ -405,30 +414,21 @@ bool gs_runner::dev_take(int64_t b, bool block) {
     using namespace gs;
     std::lock_guard<std::recursive_mutex> lk(dev_mu);
     DevStream& d = dstreams[b % cfg.n_streams];
-    const bool queued = d.nq > 0 && d.qb[0] == b;
-    if (!block && (!queued || !dsampler_run_ready(d.ds, d.qrun[0]))) return false;  // not enqueued yet (held) or running
+    const DevStream::Queued& q = d.q[0];
+    const bool queued = d.nq > 0 && q.batch == b;
+    if (!block && (!queued || !dsampler_run_ready(d.ds, q.run))) return false;  // not enqueued yet (held) or running
     GS_REQUIRE(queued, GS_EINVAL, "device sampler: batch not enqueued (past the release mark?)");
     const auto tw = Clock::now();
     DevResult& R = dres[b % n_dpack];
-    const int rc = gs_dsampler_result_of(d.ds, d.qrun[0], R.hop_sizes, R.offsets, &R.used);
-    if (rc != GS_OK) fail(rc, gs_last_error());
-    hip_ok(hipEventSynchronize(d.t1[0]), "hipEventSynchronize");
+    ok(gs_dsampler_result_of(d.ds, q.run, R.hop_sizes, R.offsets, &R.used));
+    hip_ok(hipEventSynchronize(q.t1), "hipEventSynchronize");
     float ms = 0.f;
-    hip_ok(hipEventElapsedTime(&ms, d.t0[0], d.t1[0]), "hipEventElapsedTime");
+    hip_ok(hipEventElapsedTime(&ms, q.t0, q.t1), "hipEventElapsedTime");
     R.sample_s = 1e-3 * ms;
     stats.wait_sample_s += secs(tw, Clock::now());
-    if (!d.counted[0]) sampled.fetch_add(1);
-    // pop the front: every slot moves up one, the freed events to the back
-    const hipEvent_t e0 = d.t0[0], e1 = d.t1[0];
-    for (int q = 1; q < kDevDepthMax; ++q) {
-        d.qb[q - 1] = d.qb[q];
-        d.qrun[q - 1] = d.qrun[q];
-        d.t0[q - 1] = d.t0[q];
-        d.t1[q - 1] = d.t1[q];
-        d.counted[q - 1] = d.counted[q];
-    }
-    d.t0[kDevDepthMax - 1] = e0;
-    d.t1[kDevDepthMax - 1] = e1;
+    if (!q.counted) sampled.fetch_add(1);
+    // pop the front: every element moves up one, the front with its events to the back
+    std::rotate(d.q, d.q + 1, d.q + kDevDepthMax);
     --d.nq;
     return true;
 }
@@ -437,9 +437,9 @@ bool gs_runner::dev_take(int64_t b, bool block) {
 void gs_runner::dev_poll() {
     std::lock_guard<std::recursive_mutex> lk(dev_mu);
     for (auto& d : dstreams)
-        for (int q = 0; q < d.nq; ++q)
-            if (!d.counted[q] && gs::dsampler_run_ready(d.ds, d.qrun[q])) {
-                d.counted[q] = true;
+        for (int i = 0; i < d.nq; ++i)
+            if (!d.q[i].counted && gs::dsampler_run_ready(d.ds, d.q[i].run)) {
+                d.q[i].counted = true;
                 sampled.fetch_add(1);
             }
 }
@@ -454,10 +454,8 @@ void gs_runner::dev_sync_rngs() {
         if (!d.ds) continue;
         uint32_t mt[624];
         int64_t pos = 0;
-        int rc = gs_dsampler_get_rng(d.ds, mt, &pos, d.st);
-        if (rc != GS_OK) fail(rc, gs_last_error());
-        rc = gs_rng_set_state(cfg.rngs[w], mt, pos);
-        if (rc != GS_OK) fail(rc, gs_last_error());
+        ok(gs_dsampler_get_rng(d.ds, mt, &pos, d.st));
+        ok(gs_rng_set_state(cfg.rngs[w], mt, pos));
     }
 }
 
@@ -475,14 +473,14 @@ bool gs_runner::issue(int64_t b, bool block) {
     }
     const auto tr = Clock::now();
     const int k = static_cast<int>(b % kDev);
-    wait_entry(k);  // batch b-3 done
+    RingEntry& e = ring[k];
+    wait_entry(e);  // batch b-3 done
     stats.wait_ring_s += secs(tr, Clock::now());
     if (devmode) {
         const DevResult& R = dres[b % n_dpack];
-        const int rc = gs_trainer_gather(cfg.trainer, dpack[b % n_dpack], R.hop_sizes, R.offsets, k, side);
-        if (rc != GS_OK) fail(rc, gs_last_error());
-        hip_ok(hipEventRecord(gathered[k], side), "hipEventRecord");
-        inflight[k] = {-1, static_cast<int>(b % n_dpack)};
+        ok(gs_trainer_gather(cfg.trainer, dpack[b % n_dpack], R.hop_sizes, R.offsets, k, side));
+        hip_ok(hipEventRecord(e.gathered, side), "hipEventRecord");
+        e.inflight = {-1, static_cast<int>(b % n_dpack)};
         issued = b + 1;
         // this stream's next batch, b + S, into the ring entry step b - 3 read
         // (wait_entry above saw it complete)
@@ -493,14 +491,20 @@ bool gs_runner::issue(int64_t b, bool block) {
     PackSlot& slot = streams[f.stream]->slots[f.slot];
     // the twin holds the pack since before the slot came onto `ready`; the
     // step's launches read it after this gather, both until the step is done
-    const int rc = gs_trainer_gather(cfg.trainer, slot.dev, slot.hop_sizes, slot.offsets, k, side);
-    if (rc != GS_OK) fail(rc, gs_last_error());
-    hip_ok(hipEventRecord(gathered[k], side), "hipEventRecord");
-    inflight[k] = f;
+    ok(gs_trainer_gather(cfg.trainer, slot.dev, slot.hop_sizes, slot.offsets, k, side));
+    hip_ok(hipEventRecord(e.gathered, side), "hipEventRecord");
+    e.inflight = f;
     issued = b + 1;
     return true;
 }
 
+// In this order: (1) drain the device-sampler streams, put their state back
+// into the rngs and destroy them; (2) stop and join the sampler threads;
+// (3) destroy their teams; (4) drain the copy, side and comm streams and the
+// ring's busy step events; (5) release the pinned flag and the registered
+// huge-page slots; (6) destroy events and streams and clear the trainer's
+// hooks.  The arena (gs_runner::mem) frees the device buffers after this body,
+// so after every drain.
 gs_runner::~gs_runner() {
     if (devmode) {
         for (auto& d : dstreams)
@@ -511,9 +515,9 @@ gs_runner::~gs_runner() {
         }
         for (auto& d : dstreams) {
             if (d.ds) gs_dsampler_destroy(d.ds);
-            for (int q = 0; q < kDevDepthMax; ++q) {
-                if (d.t0[q]) (void)hipEventDestroy(d.t0[q]);
-                if (d.t1[q]) (void)hipEventDestroy(d.t1[q]);
+            for (auto& q : d.q) {
+                if (q.t0) (void)hipEventDestroy(q.t0);
+                if (q.t1) (void)hipEventDestroy(q.t1);
             }
             if (d.st) (void)hipStreamDestroy(d.st);
         }
@@ -534,8 +538,8 @@ gs_runner::~gs_runner() {
     if (copy_stream) (void)hipStreamSynchronize(copy_stream);
     if (side) (void)hipStreamSynchronize(side);
     if (comm_stream) (void)hipStreamSynchronize(comm_stream);
-    for (int d = 0; d < kDev; ++d)
-        if (dev_busy[d]) (void)hipEventSynchronize(dev_done[d]);
+    for (RingEntry& e : ring)
+        if (e.busy) (void)hipEventSynchronize(e.done);
     if (done_host) (void)hipHostFree(done_host);
     for (auto& s : streams)
         for (auto& slot : s->slots) {
@@ -545,14 +549,10 @@ gs_runner::~gs_runner() {
             } else if (slot.host) {
                 (void)hipHostFree(slot.host);
             }
-            if (slot.dev) (void)hipFree(slot.dev);
         }
-    for (int32_t* p : dpack)
-        if (p) (void)hipFree(p);
-    if (roots_dev) (void)hipFree(roots_dev);
-    for (int d = 0; d < kDev; ++d) {
-        if (dev_done[d]) (void)hipEventDestroy(dev_done[d]);
-        if (gathered[d]) (void)hipEventDestroy(gathered[d]);
+    for (RingEntry& e : ring) {
+        if (e.done) (void)hipEventDestroy(e.done);
+        if (e.gathered) (void)hipEventDestroy(e.gathered);
     }
     if (cfg.trainer && comm_stream) {
         gs::trainer_set_upper_hook(cfg.trainer, {});
@@ -564,8 +564,6 @@ gs_runner::~gs_runner() {
     if (comm_stream) (void)hipStreamDestroy(comm_stream);
     if (side) (void)hipStreamDestroy(side);
     if (copy_stream) (void)hipStreamDestroy(copy_stream);
-    if (ws) (void)hipFree(ws);
-    if (clip_ws) (void)hipFree(clip_ws);
 }
 
 extern "C" {
@@ -643,11 +641,11 @@ int gs_runner_create(const gs_runner_config* cfg, gs_runner** out) {
         hip_ok(hipDeviceGetStreamPriorityRange(&lo, &hi), "hipDeviceGetStreamPriorityRange");
         hip_ok(hipStreamCreateWithPriority(&r->side, hipStreamNonBlocking, hi), "hipStreamCreateWithPriority");
     }
-    for (int d = 0; d < gs_runner::kDev; ++d) {
-        hip_ok(hipEventCreateWithFlags(&r->dev_done[d], sync_event_flags()), "hipEventCreate");
-        hip_ok(hipEventCreateWithFlags(&r->gathered[d], sync_event_flags()), "hipEventCreate");
+    for (gs_runner::RingEntry& e : r->ring) {
+        hip_ok(hipEventCreateWithFlags(&e.done, sync_event_flags()), "hipEventCreate");
+        hip_ok(hipEventCreateWithFlags(&e.gathered, sync_event_flags()), "hipEventCreate");
     }
-    hip_ok(hipMalloc(&r->clip_ws, 64 * 8 * sizeof(float)), "hipMalloc(clip ws)");
+    r->clip_ws = r->mem.alloc<float>(64 * 8);
     r->use_flag = !cfg->embed_out;
     if (r->use_flag) {
         void* hp = nullptr;
@@ -668,8 +666,7 @@ int gs_runner_create(const gs_runner_config* cfg, gs_runner** out) {
             nd = std::min<int64_t>(nn, nd + nd * per);
         }
         const int32_t k_last = r->fanouts[cfg->n_hops - 1];  // bounds every last-hop neighbourhood
-        const int rc = gs_trainer_gather_reserve(cfg->trainer, nd * r->merge, k_last > 0 ? k_last : 0);
-        if (rc != GS_OK) fail(rc, gs_last_error());
+        ok(gs_trainer_gather_reserve(cfg->trainer, nd * r->merge, k_last > 0 ? k_last : 0));
         // the fused top launch's padded hop-1 records (2-layer training, fanout <= 31)
         if (!cfg->embed_out && cfg->n_hops == 2 && !(cfg->flags & GS_SAMPLE_GCN) && r->fanouts[0] > 0)
             trainer_reserve_top(cfg->trainer, cfg->batch, r->fanouts[0]);
@@ -691,7 +688,7 @@ int gs_runner_create(const gs_runner_config* cfg, gs_runner** out) {
         const int64_t need = gs_trainer_ws_bytes(cfg->trainer, hs);
         GS_REQUIRE(need >= 0, GS_EINVAL, gs_last_error());
         r->ws_bytes = need + (1 << 20);
-        hip_ok(hipMalloc(&r->ws, r->ws_bytes), "hipMalloc(ws)");
+        r->ws = r->mem.alloc<char>(r->ws_bytes);
     }
     const int32_t S = cfg->n_streams;
     r->devmode = cfg->device_sampler != 0;
@@ -704,40 +701,34 @@ int gs_runner_create(const gs_runner_config* cfg, gs_runner** out) {
             GS_REQUIRE(r->roots[i] >= 0 && r->roots[i] < (int64_t(1) << 31), GS_ERANGE, "root id out of range");
             r32[i] = static_cast<int32_t>(r->roots[i]);
         }
-        hip_ok(hipMalloc(&r->roots_dev, r32.size() * sizeof(int32_t)), "hipMalloc(roots)");
-        hip_ok(hipMemcpy(r->roots_dev, r32.data(), r32.size() * sizeof(int32_t), hipMemcpyHostToDevice), "hipMemcpy");
+        r->roots_dev = static_cast<int32_t*>(r->mem.upload(r32.data(), r32.size() * sizeof(int32_t)));
         r->dstreams.resize(S);
         for (int32_t w = 0; w < S; ++w) {
             gs_runner::DevStream& d = r->dstreams[w];
             hip_ok(hipStreamCreateWithFlags(&d.st, hipStreamNonBlocking), "hipStreamCreate(dsampler)");
-            for (int q = 0; q < gs_runner::kDevDepthMax; ++q) {
-                hip_ok(hipEventCreate(&d.t0[q]), "hipEventCreate");
-                hip_ok(hipEventCreate(&d.t1[q]), "hipEventCreate");
+            for (auto& q : d.q) {
+                hip_ok(hipEventCreate(&q.t0), "hipEventCreate");
+                hip_ok(hipEventCreate(&q.t1), "hipEventCreate");
             }
-            int rc = gs_dsampler_create(cfg->graph, r->fanouts.data(), cfg->n_hops, cfg->batch,
-                                        (cfg->flags & (GS_SAMPLE_GCN | GS_SAMPLE_FAIL_EMPTY)) |
-                                            (fast ? GS_DSAMPLER_FAST : S > 1 ? GS_DSAMPLER_NO_AUX : 0),
-                                        &d.ds);
-            if (rc != GS_OK) fail(rc, gs_last_error());
+            ok(gs_dsampler_create(cfg->graph, r->fanouts.data(), cfg->n_hops, cfg->batch,
+                                  (cfg->flags & (GS_SAMPLE_GCN | GS_SAMPLE_FAIL_EMPTY)) |
+                                      (fast ? GS_DSAMPLER_FAST : S > 1 ? GS_DSAMPLER_NO_AUX : 0),
+                                  &d.ds));
             d.next = w;
             if (fast) {
-                rc = gs_dsampler_set_seed(d.ds, cfg->sampler_seed);
-                if (rc != GS_OK) fail(rc, gs_last_error());
+                ok(gs_dsampler_set_seed(d.ds, cfg->sampler_seed));
                 continue;
             }
             uint32_t mt[624];
             int64_t pos = 0;
-            rc = gs_rng_get_state(cfg->rngs[w], mt, &pos);
-            if (rc != GS_OK) fail(rc, gs_last_error());
-            rc = gs_dsampler_set_rng(d.ds, mt, pos, d.st);
-            if (rc != GS_OK) fail(rc, gs_last_error());
-            d.next = w;
+            ok(gs_rng_get_state(cfg->rngs[w], mt, &pos));
+            ok(gs_dsampler_set_rng(d.ds, mt, pos, d.st));
         }
         r->dcap = std::max<int64_t>(r->cap, gs_dsampler_pack_bound(r->dstreams[0].ds, cfg->batch));
         r->dev_depth = gs_runner::kDevDepthMax;
         r->n_dpack = r->dev_depth * S + 3;
         r->dpack.assign(r->n_dpack, nullptr);
-        for (auto& p : r->dpack) hip_ok(hipMalloc(&p, r->dcap * sizeof(int32_t)), "hipMalloc(pack)");
+        for (auto& p : r->dpack) p = r->mem.alloc<int32_t>(r->dcap);
         r->dres.resize(r->n_dpack);
     }
     // GS_SHARED_HELPERS=1: one pool of S x helpers threads behind all the
@@ -777,7 +768,7 @@ int gs_runner_create(const gs_runner_config* cfg, gs_runner** out) {
                 sl.thp_bytes = bytes;
                 hip_ok(hipHostRegister(sl.host, bytes, hipHostRegisterDefault), "hipHostRegister(pack slot)");
             }
-            hip_ok(hipMalloc(&sl.dev, r->cap * sizeof(int32_t)), "hipMalloc(pack twin)");
+            sl.dev = r->mem.alloc<int32_t>(r->cap);
             s->free.push_back(q);
         }
         r->streams.push_back(std::move(s));
@@ -794,9 +785,7 @@ int gs_runner_create(const gs_runner_config* cfg, gs_runner** out) {
             const int64_t n = gs_trainer_n_params(rp->cfg.trainer);
             hip_ok(hipEventRecord(rp->upper_ready, st), "hipEventRecord");
             hip_ok(hipStreamWaitEvent(rp->comm_stream, rp->upper_ready, 0), "hipStreamWaitEvent");
-            const int rc = gs_comm_allreduce_sum(rp->cfg.comm, gs_trainer_grads(rp->cfg.trainer) + w1, n - w1,
-                                                 rp->comm_stream);
-            if (rc != GS_OK) fail(rc, gs_last_error());
+            ok(gs_comm_allreduce_sum(rp->cfg.comm, gs_trainer_grads(rp->cfg.trainer) + w1, n - w1, rp->comm_stream));
         });
         const char* ch_env = std::getenv("GS_AR_W1_CHUNKS");
         const int chunks = ch_env ? std::atoi(ch_env) : 2;
@@ -807,9 +796,7 @@ int gs_runner_create(const gs_runner_config* cfg, gs_runner** out) {
                 // the collectives on one communicator in one stream order
                 hip_ok(hipEventRecord(rp->w1_ready, st), "hipEventRecord");
                 hip_ok(hipStreamWaitEvent(rp->comm_stream, rp->w1_ready, 0), "hipStreamWaitEvent");
-                const int rc = gs_comm_allreduce_sum(rp->cfg.comm, gs_trainer_grads(rp->cfg.trainer) + off, n,
-                                                     rp->comm_stream);
-                if (rc != GS_OK) fail(rc, gs_last_error());
+                ok(gs_comm_allreduce_sum(rp->cfg.comm, gs_trainer_grads(rp->cfg.trainer) + off, n, rp->comm_stream));
                 ++rp->w1_issued;
             });
         }
@@ -848,10 +835,10 @@ int gs_runner_run(gs_runner* r, int64_t n_steps, float* loss, void* stream) {
         ~Unwind() {
             gs::trainer_set_done(r->cfg.trainer, nullptr, 0);  // never left for a later step of this trainer
             if (!armed) return;
-            for (int k = 0; k < gs_runner::kDev; ++k)
-                if (r->flag_step[k] >= 0 && hipEventRecord(r->dev_done[k], st) == hipSuccess) {
-                    r->flag_step[k] = -1;
-                    r->dev_busy[k] = true;
+            for (gs_runner::RingEntry& e : r->ring)
+                if (e.flag_step >= 0 && hipEventRecord(e.done, st) == hipSuccess) {
+                    e.flag_step = -1;
+                    e.busy = true;
                 }
         }
     } unwind{r, st};
@@ -897,11 +884,12 @@ int gs_runner_run(gs_runner* r, int64_t n_steps, float* loss, void* stream) {
         // this step (never block here: with a slow sampler that would idle the GPU)
         if (b + 1 < r->n_units && r->issued == b + 1) r->issue(b + 1, false);
         const int k = static_cast<int>(b % gs_runner::kDev);
+        gs_runner::RingEntry& e = r->ring[k];
         const auto tg = Clock::now();
-        hip_ok(hipEventSynchronize(r->gathered[k]), "hipEventSynchronize");  // normally long done
+        hip_ok(hipEventSynchronize(e.gathered), "hipEventSynchronize");  // normally long done
         const auto t1 = Clock::now();
         r->stats.wait_gather_s += secs(tg, t1);
-        const gs::Inflight f = r->inflight[k];
+        const gs::Inflight f = e.inflight;
         const int64_t* hop_sizes;
         const int64_t* offsets;
         int64_t used;
@@ -924,31 +912,27 @@ int gs_runner_run(gs_runner* r, int64_t n_steps, float* loss, void* stream) {
         GS_REQUIRE(need >= 0, GS_EINVAL, gs_last_error());
         if (need > r->ws_bytes) {
             hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize");
-            if (r->ws) hip_ok(hipFree(r->ws), "hipFree");
-            r->ws = nullptr;
-            r->ws_bytes = need + need / 4 + (1 << 20);
-            hip_ok(hipMalloc(&r->ws, r->ws_bytes), "hipMalloc(ws)");
+            r->ws_bytes = 0;  // (what is held, should the larger one be refused)
+            r->mem.release(std::exchange(r->ws, nullptr));
+            const int64_t grown = need + need / 4 + (1 << 20);
+            r->ws = r->mem.alloc<char>(grown);
+            r->ws_bytes = grown;
         }
         const int64_t pack_total = used - r->cfg.batch;
         bool consumed_flag = false;
         int32_t* pk = r->devmode ? r->dpack[f.slot] : r->streams[f.stream]->slots[f.slot].dev;
         auto t3 = Clock::now();
         if (r->cfg.embed_out) {  // inference: the forward into this batch's output rows
-            const int rc = gs_trainer_forward_gathered(r->cfg.trainer, pk, hop_sizes, offsets, k, r->ws,
-                                                       r->ws_bytes,
-                                                       r->cfg.embed_out + b * r->merge * r->cfg.batch * r->cfg.embed_ld,
-                                                       st);
-            if (rc != GS_OK) fail(rc, gs_last_error());
+            ok(gs_trainer_forward_gathered(r->cfg.trainer, pk, hop_sizes, offsets, k, r->ws, r->ws_bytes,
+                                           r->cfg.embed_out + b * r->merge * r->cfg.batch * r->cfg.embed_ld, st));
             t3 = Clock::now();
         } else {
             // the done flag goes to the step's SGD launch: the fused slab sum
             // inside the step, or gs_trainer_update* below
             if (r->use_flag) trainer_set_done(r->cfg.trainer, r->done_dev, b);
             r->w1_issued = 0;
-            int rc = gs_trainer_forward_backward_gathered(r->cfg.trainer, pk, hop_sizes, offsets,
-                                                          pk + pack_total, r->cfg.batch, k, r->ws, r->ws_bytes, loss,
-                                                          st);
-            if (rc != GS_OK) fail(rc, gs_last_error());
+            ok(gs_trainer_forward_backward_gathered(r->cfg.trainer, pk, hop_sizes, offsets, pk + pack_total,
+                                                    r->cfg.batch, k, r->ws, r->ws_bytes, loss, st));
             t3 = Clock::now();
             // with a communicator (any world size, so one rank exercises the same
             // path): sum the gradients, then clip the averaged sum; without one
@@ -961,30 +945,28 @@ int gs_runner_run(gs_runner* r, int64_t n_steps, float* loss, void* stream) {
                 if (r->w1_issued == 0) {  // W1 in one piece (the trainer's unchunked path)
                     hip_ok(hipEventRecord(r->upper_ready, st), "hipEventRecord");  // dW1 final
                     hip_ok(hipStreamWaitEvent(r->comm_stream, r->upper_ready, 0), "hipStreamWaitEvent");
-                    rc = gs_comm_allreduce_sum(r->cfg.comm, grads, trainer_w1_floats(r->cfg.trainer), r->comm_stream);
-                    if (rc != GS_OK) fail(rc, gs_last_error());
+                    ok(gs_comm_allreduce_sum(r->cfg.comm, grads, trainer_w1_floats(r->cfg.trainer), r->comm_stream));
                 }
                 hip_ok(hipEventRecord(r->upper_reduced, r->comm_stream), "hipEventRecord");
                 hip_ok(hipStreamWaitEvent(st, r->upper_reduced, 0), "hipStreamWaitEvent");
             } else if (r->cfg.comm) {
-                rc = gs_comm_allreduce_sum(r->cfg.comm, grads, n_params, st);
-                if (rc != GS_OK) fail(rc, gs_last_error());
+                ok(gs_comm_allreduce_sum(r->cfg.comm, grads, n_params, st));
             }
-            rc = r->cfg.comm
-                     ? gs_trainer_update(r->cfg.trainer, 1.0f / static_cast<float>(r->cfg.world), r->clip_ws, st)
-                     : gs_trainer_update_local(r->cfg.trainer, st);
+            const int rc =
+                r->cfg.comm ? gs_trainer_update(r->cfg.trainer, 1.0f / static_cast<float>(r->cfg.world), r->clip_ws, st)
+                            : gs_trainer_update_local(r->cfg.trainer, st);
             consumed_flag = r->use_flag && trainer_done_taken(r->cfg.trainer);
             trainer_set_done(r->cfg.trainer, nullptr, 0);
-            if (rc != GS_OK) fail(rc, gs_last_error());
+            ok(rc);
         }
-        r->entry_batch[k] = b;
+        e.batch = b;
         if (consumed_flag) {
-            r->flag_step[k] = b;  // its SGD signals the entry free
-            r->dev_busy[k] = false;
+            e.flag_step = b;  // its SGD signals the entry free
+            e.busy = false;
         }
         if (!consumed_flag || step + 1 == n_steps) {
-            hip_ok(hipEventRecord(r->dev_done[k], st), "hipEventRecord");  // ring entry k free again
-            r->dev_busy[k] = true;
+            hip_ok(hipEventRecord(e.done, st), "hipEventRecord");  // ring entry k free again
+            e.busy = true;
         }
         for (int q = 0; q < 4 * GS_MAX_HOPS; ++q) r->stats.hop_sizes[q] += static_cast<double>(hop_sizes[q]);
         r->stats.sample_s += sample_s;
