@@ -122,6 +122,8 @@ _SIGS = {
     "gs_unsup_destroy": (None, [_vp]),
     "gs_unsup_attach_device": (_i32, [_vp, _vp]),
     "gs_unsup_extend": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp]),
+    "gs_unsup_extend_fast": (_i32, [_vp, _u64, _i64, _vp, _i64, _i64, _i32, _i32, _vp]),
+    "gs_unsup_fast_phases": (_i32, [_vp, _i32, _vp]),
     "gs_unsup_fetch": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gs_unsup_loss_plan": (_i32, [_vp, _vp, _i64, _vp, _p(_i64)]),
     "gs_unsup_loss_ws_floats": (_i64, [_i64, _i64, _i64]),

@@ -22,6 +22,11 @@
 //              parallel (no rng); the draws then run in node order on the
 //              one stream.
 //   unique     models.py:146  list(set(flat positives) | set(flat negatives)).
+//
+// gs_unsup_extend_fast is the opt-in extend without that parity:
+// Philox words by (seed, batch index, position, draw), far lists and the unique
+// list in ascending id order.  Its sequential host mirror is below
+// (extend_fast_host); kernels/unsup_fast.hip is the device path.
 #include <algorithm>
 #include <atomic>
 #include <memory>
@@ -34,6 +39,7 @@
 
 #include "common.hpp"
 #include "graph.hpp"
+#include "philox.hpp"
 #include "pyset.hpp"
 #include "team.hpp"
 #include "rng.hpp"
@@ -117,6 +123,7 @@ struct gs_unsup {
     std::vector<uint8_t> is_train;      // [n_nodes]
     std::vector<int32_t> train_order;   // list(set(train_nodes))
     std::vector<int32_t> copy_order;    // list(set(train_nodes).copy())
+    std::vector<int32_t> asc_order;     // sorted(set(train_nodes)): the far order of the counter-based extend
     int64_t n_train_set = 0;
     gs::BallSet balls;                  // the chunk's 5-hop balls
     // last extend_nodes
@@ -427,9 +434,150 @@ void negative_pairs_dev(gs_unsup& u, gs_rng* rng, int64_t num_neg, int32_t n_thr
 }
 #endif
 
+
+// ---------------------------------------------------------------------------
+// The counter-based extend, host mirror: the rule stated
+// sequentially, the CPU reference of kernels/unsup_fast.hip.  No rng state, no
+// CPython set order: every random word is draw_word(seed, batch_index, r, tag,
+// t) with r the node's position in the batch.
+void extend_fast_host(gs_unsup& u, uint64_t seed, uint64_t bi, int64_t num_neg, int32_t parts, int32_t n_threads) {
+    const gs::Graph& g = *u.g;
+    const int64_t n = static_cast<int64_t>(u.nodes.size());
+    if (parts & 1)
+        for (int64_t i = 0; i < n; ++i) {
+            const int64_t v = u.nodes[i];
+            if (g.degree(v) == 0) continue;
+            u.has_pos[i] = 1;
+            for (int32_t w = 0; w < u.n_walks; ++w) {
+                int64_t cur = v;
+                for (int32_t j = 0; j < u.walk_len; ++j) {
+                    const int64_t d = g.degree(cur);
+                    if (d == 0) break;  // a dead end (directed input only) stops the walk
+                    const uint32_t word = gs::fs::draw_word(seed, bi, static_cast<uint32_t>(i), gs::kFastHopWalk,
+                                                            static_cast<uint32_t>(w * u.walk_len + j));
+                    const int64_t nxt = g.col[g.row_ptr[cur] + gs::fs::randbelow(static_cast<uint32_t>(d), word)];
+                    if (nxt != v && u.is_train[nxt]) {
+                        u.pos.push_back(v);
+                        u.pos.push_back(nxt);
+                        ++u.pos_cnt[i];
+                    }
+                    cur = nxt;
+                }
+            }
+        }
+    if (parts & 2) {
+        // roots per ball chunk: whole words, ~96 MiB of ball bitmaps at most (as negative_pairs)
+        const int64_t words = std::max<int64_t>(1, std::min<int64_t>(16, (int64_t(96) << 20) / (24 * g.n_nodes + 1)));
+        const int64_t chunk = 64 * words;
+        std::vector<int64_t> ball_size;
+        std::vector<int32_t> far, chosen;
+        for (int64_t c0 = 0; c0 < n; c0 += chunk) {
+            const int64_t cn = std::min(chunk, n - c0);
+            u.balls.grow(g, u.nodes.data() + c0, cn, u.n_walk_len, std::max<int32_t>(1, n_threads), ball_size);
+            for (int64_t j = 0; j < cn; ++j) {
+                const int64_t i = c0 + j, v = u.nodes[i];
+                far.clear();
+                for (int32_t x : u.asc_order)
+                    if (!u.balls.has(j, x)) far.push_back(x);
+                const int64_t len = static_cast<int64_t>(far.size());
+                if (num_neg < len) {  // Floyd's algorithm, k = num_neg over [0, len)
+                    chosen.clear();
+                    for (int64_t t = 0; t < num_neg; ++t) {
+                        const uint32_t m = static_cast<uint32_t>(len - num_neg + t);
+                        const uint32_t word = gs::fs::draw_word(seed, bi, static_cast<uint32_t>(i), gs::kFastHopNeg,
+                                                                static_cast<uint32_t>(t));
+                        const int32_t x = static_cast<int32_t>(gs::fs::randbelow(m + 1u, word));
+                        const bool taken = std::find(chosen.begin(), chosen.end(), x) != chosen.end();
+                        chosen.push_back(taken ? static_cast<int32_t>(m) : x);
+                    }
+                    for (int32_t pk : chosen) {
+                        u.neg.push_back(v);
+                        u.neg.push_back(far[static_cast<size_t>(pk)]);
+                    }
+                    u.neg_cnt[i] = num_neg;
+                } else {
+                    for (int32_t x : far) {
+                        u.neg.push_back(v);
+                        u.neg.push_back(x);
+                    }
+                    u.neg_cnt[i] = len;
+                }
+            }
+        }
+    }
+    // unique_nodes_batch: the distinct pair members, ascending
+    u.unique = u.pos;
+    u.unique.insert(u.unique.end(), u.neg.begin(), u.neg.end());
+    std::sort(u.unique.begin(), u.unique.end());
+    u.unique.erase(std::unique(u.unique.begin(), u.unique.end()), u.unique.end());
+}
+
+// set(target) < set(unique) (models.py:147) over an ascending unique list:
+// every target present and the list strictly longer than the distinct targets.
+// One definition for the host mirror and the device path.
+bool fast_subset_ok(const gs_unsup& u) {
+    std::vector<int64_t> tgt(u.nodes);
+    std::sort(tgt.begin(), tgt.end());
+    tgt.erase(std::unique(tgt.begin(), tgt.end()), tgt.end());
+    if (u.unique.size() <= tgt.size()) return false;
+    for (int64_t x : tgt)
+        if (!std::binary_search(u.unique.begin(), u.unique.end(), x)) return false;
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
+
+int gs_unsup_extend_fast(gs_unsup* u, uint64_t seed, int64_t batch_index, const int64_t* nodes, int64_t n,
+                         int64_t num_neg, int32_t parts, int32_t n_threads, int64_t* sizes) {
+    GS_API_BEGIN
+    GS_REQUIRE(u && sizes && (nodes || n == 0) && n >= 0, GS_EINVAL, "bad arguments");
+    GS_REQUIRE(num_neg >= 0, GS_ERANGE, "Sample larger than population or is negative");
+    GS_REQUIRE(num_neg <= gs::kFastMaxNeg, GS_EINVAL, "extend=fast: num_neg above 1024");
+    GS_REQUIRE(parts >= 1 && parts <= 3, GS_EINVAL, "parts: 1 walks, 2 negatives, 3 both");
+    const int64_t slots = static_cast<int64_t>(u->n_walks) * u->walk_len;
+    GS_REQUIRE(slots <= gs::kFastMaxWalkDraws, GS_EINVAL, "extend=fast: N_WALKS * WALK_LEN above 65536");
+    GS_REQUIRE(n * (slots + num_neg + 1) < (int64_t(1) << 30), GS_ERANGE, "extend=fast: batch too large");
+    const gs::Graph& g = *u->g;
+    for (int64_t i = 0; i < n; ++i) GS_REQUIRE(nodes[i] >= 0 && nodes[i] < g.n_nodes, GS_ERANGE, "node id out of range");
+    u->nodes.assign(nodes, nodes + n);
+    u->pos.clear();
+    u->neg.clear();
+    u->unique.clear();
+    u->pos_cnt.assign(n, 0);
+    u->neg_cnt.assign(n, 0);
+    u->has_pos.assign(n, 0);
+    u->subset_ok = 0;
+#ifndef GS_HOST_ONLY
+    if (u->dev) {
+        const gs::FastExtend a{seed, batch_index, u->n_walks, u->walk_len, u->n_walk_len, num_neg, parts};
+        gs::unsup_dev_extend_fast(u->dev, g, u->is_train, a, u->nodes, u->unique, u->pos, u->neg, u->pos_cnt,
+                                  u->neg_cnt, u->has_pos);
+    } else
+#endif
+        extend_fast_host(*u, seed, static_cast<uint64_t>(batch_index), num_neg, parts, n_threads);
+    u->subset_ok = fast_subset_ok(*u) ? 1 : 0;
+    sizes[0] = static_cast<int64_t>(u->unique.size());
+    sizes[1] = static_cast<int64_t>(u->pos.size() / 2);
+    sizes[2] = static_cast<int64_t>(u->neg.size() / 2);
+    sizes[3] = u->subset_ok;
+    GS_API_END
+}
+
+int gs_unsup_fast_phases(gs_unsup* u, int32_t enable, double* ms) {
+    GS_API_BEGIN
+    GS_REQUIRE(u, GS_EINVAL, "NULL argument");
+#ifdef GS_HOST_ONLY
+    (void)enable;
+    (void)ms;
+    gs::fail(GS_EINVAL, "host-only build: no device");
+#else
+    GS_REQUIRE(u->dev, GS_EINVAL, "gs_unsup_fast_phases: no device attached");
+    gs::unsup_dev_fast_phases(u->dev, enable, ms);
+#endif
+    GS_API_END
+}
 
 int gs_unsup_attach_device(gs_unsup* u, void* stream) {
     GS_API_BEGIN
@@ -464,6 +612,8 @@ int gs_unsup_create(const gs_graph* graph, const int64_t* train_nodes, int64_t n
     u->n_train_set = ts.used;
     ts.for_each([&](int32_t x) { u->train_order.push_back(x); });
     gs::copy_of(ts).for_each([&](int32_t x) { u->copy_order.push_back(x); });
+    u->asc_order = u->copy_order;
+    std::sort(u->asc_order.begin(), u->asc_order.end());
     *out = u.release();
     GS_API_END
 }

@@ -28,4 +28,27 @@ void unsup_dev_select(UnsupDev* d, const std::vector<int32_t>& req_r, const std:
 void unsup_dev_far_lists(UnsupDev* d, const std::vector<int32_t>& balls, const std::vector<int64_t>& base,
                          std::vector<int32_t>& out);
 
+// The counter-based extend (kernels/unsup_fast.hip) of `nodes`,
+// whole on the device half's stream: the outputs are gs_unsup's members of the
+// same names, sized by the call.  Two host synchronisations (the sizes, then
+// the arrays); n == 0 launches nothing.
+constexpr uint32_t kFastHopWalk = 0xF0u, kFastHopNeg = 0xF1u;  // draw_word's hop tags (the sampler's are 1..3)
+constexpr int kFastMaxNeg = 1024;        // num_neg: the chosen list of a node lives in LDS
+constexpr int kFastMaxWalkDraws = 65536; // n_walks * walk_len
+struct FastExtend {
+    uint64_t seed;
+    int64_t batch_index;
+    int32_t n_walks, walk_len, n_walk_len;
+    int64_t num_neg;
+    int32_t parts;
+};
+void unsup_dev_extend_fast(UnsupDev* d, const Graph& g, const std::vector<uint8_t>& is_train, const FastExtend& a,
+                           const std::vector<int64_t>& nodes, std::vector<int64_t>& unique, std::vector<int64_t>& pos,
+                           std::vector<int64_t>& neg, std::vector<int64_t>& pos_cnt, std::vector<int64_t>& neg_cnt,
+                           std::vector<uint8_t>& has_pos);
+// Device-event times of the last fast extend's phases (walks, balls, masks,
+// negatives, unique, copy-back; ms[6], NULL skips) and whether the next calls
+// record them.
+void unsup_dev_fast_phases(UnsupDev* d, int enable, double* ms);
+
 }  // namespace gs

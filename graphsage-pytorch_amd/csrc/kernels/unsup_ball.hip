@@ -22,8 +22,8 @@
 
 #include "../host/graph.hpp"
 #include "../host/unsup_dev.hpp"
-#include "dev_host.hpp"
 #include "kcommon.hpp"
+#include "unsup_dev_state.hpp"
 
 namespace gs {
 namespace {
@@ -203,44 +203,6 @@ __global__ __launch_bounds__(64) void far_list_kernel(const int32_t* __restrict_
 
 }  // namespace
 
-struct UnsupDev {
-    int64_t n_nodes = 0;
-    int n_order = 0, n_chunks = 0;
-    DevArena mem{"unsup dev"};
-    const int64_t* t_ptr = nullptr;  // transposed CSR (in-neighbours) for the pulls
-    const int32_t* t_col = nullptr;
-    int32_t* copy_order = nullptr;  // list(set(train).copy())
-    int32_t* asc_order = nullptr;   // sorted(set(train))
-    int32_t* set_order = nullptr;   // list(set(train))
-    int cap_roots = 0;
-    unsigned long long *S = nullptr, *E = nullptr, *X = nullptr;
-    int32_t* roots = nullptr;
-    int64_t* counts = nullptr;  // [2][cap_roots]
-    unsigned long long* M[3] = {};
-    int32_t* pre[3] = {};
-    int cap_req = 0;
-    int32_t *req_r = nullptr, *req_j = nullptr, *picks = nullptr;
-    int cap_lists = 0;
-    int64_t cap_list_out = 0;
-    int32_t* list_balls = nullptr;
-    int64_t* list_base = nullptr;
-    int32_t* list_out = nullptr;
-    uint8_t* req_kind = nullptr;
-    hipStream_t st = nullptr;
-
-    // A grown buffer replaces the old one, which is freed at once: every call
-    // ends with a stream synchronise, so no launch still reads it.
-    template <typename T>
-    void regrow(T*& p, int64_t n) {
-        if (p) mem.release(p);
-        p = mem.alloc<T>(n);
-    }
-    ~UnsupDev() {  // `mem` frees the buffers after this body
-        if (st) (void)hipStreamSynchronize(st);
-        if (st) (void)hipStreamDestroy(st);
-    }
-};
-
 // The device half owns a non-blocking stream on the current device: its calls
 // synchronise only their own work (not the caller's queued model launches, so
 // the host can draw while the previous step's backward runs) and never depend
@@ -275,7 +237,7 @@ UnsupDev* unsup_dev_create(const Graph& g, const std::vector<int32_t>& copy_orde
 
 void unsup_dev_destroy(UnsupDev* d) { delete d; }
 
-static void reserve_roots(UnsupDev* d, int n) {
+void unsup_dev_reserve_roots(UnsupDev* d, int n) {
     if (n <= d->cap_roots) return;
     const int cap = std::max(n, 64);
     const int64_t words = (cap + 63) / 64;
@@ -291,14 +253,10 @@ static void reserve_roots(UnsupDev* d, int n) {
     d->cap_roots = cap;
 }
 
-void unsup_dev_balls(UnsupDev* d, const int64_t* nodes, int n, int hops, int64_t* ball_size, int64_t* train_in_ball) {
-    if (n <= 0) return;  // no balls: no launch (a zero-block grid is an error)
-    reserve_roots(d, n);
+void unsup_dev_launch_balls(UnsupDev* d, int n, int hops, bool counts) {
     const int n_words = (n + 63) / 64;
     const int64_t total = static_cast<int64_t>(n_words) * d->n_nodes;
-    std::vector<int32_t> r32(nodes, nodes + n);
     hipStream_t st = d->st;
-    hip_ok(hipMemcpyAsync(d->roots, r32.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
     hip_ok(hipMemsetAsync(d->S, 0, total * 8, st), "hipMemsetAsync");
     hip_ok(hipMemsetAsync(d->E, 0, total * 8, st), "hipMemsetAsync");
     ball_seed_kernel<<<(n + 255) / 256, 256, 0, st>>>(d->roots, n, d->n_nodes, d->S, d->E);
@@ -310,21 +268,37 @@ void unsup_dev_balls(UnsupDev* d, const int64_t* nodes, int n, int hops, int64_t
         check_launch("ball_pull_kernel");
         std::swap(cur, next);
     }
+    if (!counts) return;
     // >= ~512 blocks however few words the batch has
     const unsigned slices = static_cast<unsigned>(std::min(64, std::max(1, (512 + n_words - 1) / n_words)));
     hip_ok(hipMemsetAsync(d->counts, 0, 2 * static_cast<size_t>(d->cap_roots) * sizeof(int64_t), st), "hipMemsetAsync");
     ball_count_kernel<<<dim3(static_cast<unsigned>(n_words), slices), 256, 0, st>>>(
         d->S, d->n_nodes, d->asc_order, d->n_order, n, d->counts, d->counts + d->cap_roots);
     check_launch("ball_count_kernel");
-    // far masks and their prefixes for the three orders (needed by the picks)
+}
+
+void unsup_dev_launch_masks(UnsupDev* d, int n, int lo, int hi) {
+    const int n_words = (n + 63) / 64;
+    hipStream_t st = d->st;
     const dim3 mg(static_cast<unsigned>(d->n_chunks), static_cast<unsigned>(n_words));
     const int32_t* orders[3] = {d->copy_order, d->asc_order, d->set_order};
-    for (int o = 0; o < 3; ++o) {
+    for (int o = lo; o < hi; ++o) {
         far_mask_kernel<<<mg, 64, 0, st>>>(d->S, d->n_nodes, orders[o], d->n_order, d->n_chunks, n, d->M[o], d->pre[o]);
         check_launch("far_mask_kernel");
         far_prefix_kernel<<<n, 64, 0, st>>>(d->pre[o], d->n_chunks);
         check_launch("far_prefix_kernel");
     }
+}
+
+void unsup_dev_balls(UnsupDev* d, const int64_t* nodes, int n, int hops, int64_t* ball_size, int64_t* train_in_ball) {
+    if (n <= 0) return;  // no balls: no launch (a zero-block grid is an error)
+    unsup_dev_reserve_roots(d, n);
+    std::vector<int32_t> r32(nodes, nodes + n);
+    hipStream_t st = d->st;
+    hip_ok(hipMemcpyAsync(d->roots, r32.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
+    unsup_dev_launch_balls(d, n, hops, true);
+    // far masks and their prefixes for the three orders (needed by the picks)
+    unsup_dev_launch_masks(d, n, 0, 3);
     hip_ok(hipMemcpyAsync(ball_size, d->counts, n * sizeof(int64_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
     hip_ok(hipMemcpyAsync(train_in_ball, d->counts + d->cap_roots, n * sizeof(int64_t), hipMemcpyDeviceToHost, st),
            "hipMemcpyAsync");

@@ -11,6 +11,12 @@ backward into the embedding rows.
 The pair containers the reference exposes (``positive_pairs``,
 ``negtive_pairs``, ``node_positive_pairs``, ``node_negtive_pairs``) are built
 lazily from the native arrays on first access.
+
+``extend="fast"`` gives up that parity: walks, negatives and
+``unique_nodes_batch`` become a pure function of (seed, ``batch_index``, the
+batch) drawn from Philox counters, computed whole on the device
+(kernels/unsup_fast.hip) or by the sequential host mirror; Python's ``random``
+is never touched.
 """
 import ctypes
 import os
@@ -71,9 +77,25 @@ class UnsupervisedLoss:
     ``device_balls``: grow extend_nodes' 5-hop balls and pick the far-list
     negatives on the GPU (gs_unsup_attach_device; same results and stream);
     default: when ``device`` is a HIP device and the graph has at least
-    DEVICE_BALLS_MIN_NODES ids (``device_balls_default``)."""
+    DEVICE_BALLS_MIN_NODES ids (``device_balls_default``).
+    ``extend``: "exact" (the default, above) or "fast", the counter-based rule
+    of DESIGN §5e: every extend is a pure function of (``seed``,
+    ``batch_index``, nodes, num_neg) and no ``random`` stream is read.
+    ``batch_index`` starts at 0, may be set, and extend_nodes /
+    extend_nodes_array advance it by one per call.  Under "fast" the device
+    half is attached whenever ``device`` is a HIP device (``device_balls=False``
+    selects the host mirror, which gives the same bits); num_neg above 1024 is
+    a ValueError, and ``rng=`` makes no sense and is refused."""
 
-    def __init__(self, adj_lists, train_nodes, device, *, rng=None, n_threads=None, device_balls=None):
+    def __init__(self, adj_lists, train_nodes, device, *, rng=None, n_threads=None, device_balls=None,
+                 extend="exact", seed=0):
+        if extend not in ("exact", "fast"):
+            raise ValueError("UnsupervisedLoss: extend must be 'exact' or 'fast'")
+        if extend == "fast" and rng is not None:
+            raise ValueError("UnsupervisedLoss: extend='fast' draws from (seed, batch_index), not from an rng")
+        self.extend = extend
+        self.seed = int(seed) & (2 ** 64 - 1)
+        self.batch_index = 0
         self.Q = 10
         self.N_WALKS = 6
         self.WALK_LEN = 1
@@ -95,8 +117,12 @@ class UnsupervisedLoss:
             tr = np.asarray(train_nodes, np.int64).reshape(-1)
             n = max(max(keys, default=-1), int(tr.max(initial=-1))) + 1
             self.graph = CSRGraph.from_adj_lists(adj_lists, n_nodes=n)
-        self.device_balls = (device_balls_default(dev, self.graph.n_nodes) if device_balls is None
-                             else bool(device_balls))
+        if device_balls is not None:
+            self.device_balls = bool(device_balls)
+        elif extend == "fast":
+            self.device_balls = dev.type == "cuda"
+        else:
+            self.device_balls = device_balls_default(dev, self.graph.n_nodes)
         self._h = None
         self._make_handle()
 
@@ -120,14 +146,18 @@ class UnsupervisedLoss:
             lib().gs_unsup_destroy(self._h)
             self._make_handle()
         nodes = np.ascontiguousarray(np.asarray(nodes, np.int64).reshape(-1))
-        rng = self.rng if self.rng is not None else RNG.from_python(_pyrandom)
         sizes = np.zeros(4, np.int64)
-        try:
-            check(lib().gs_unsup_extend(self._h, rng._h, ptr(nodes), len(nodes), int(num_neg), parts,
-                                        self.n_threads, ptr(sizes)))
-        finally:
-            if self.rng is None:
-                rng.to_python(_pyrandom)
+        if self.extend == "fast":
+            check(lib().gs_unsup_extend_fast(self._h, self.seed, int(self.batch_index), ptr(nodes), len(nodes),
+                                             int(num_neg), parts, self.n_threads, ptr(sizes)))
+        else:
+            rng = self.rng if self.rng is not None else RNG.from_python(_pyrandom)
+            try:
+                check(lib().gs_unsup_extend(self._h, rng._h, ptr(nodes), len(nodes), int(num_neg), parts,
+                                            self.n_threads, ptr(sizes)))
+            finally:
+                if self.rng is None:
+                    rng.to_python(_pyrandom)
         U, P, N, ok = (int(x) for x in sizes)
         uniq = np.zeros(max(U, 1), np.int64)
         pos = np.zeros((max(P, 1), 2), np.int64)
@@ -232,6 +262,8 @@ class UnsupervisedLoss:
         self._reset_pairs()
         self.target_nodes = nodes
         r = self._run(nodes, num_neg, PARTS_BOTH)
+        if self.extend == "fast":
+            self.batch_index += 1
         self._pos_parts, self._neg_parts = [r], [r]
         self._last = r
         self._uniq_arr, self._uniq_list = r["unique"], None
@@ -294,6 +326,13 @@ class UnsupervisedLoss:
     def get_loss_margin(self, embeddings, nodes):
         """models.py:98-132."""
         return self._loss(embeddings, nodes, KIND_MARGIN)
+
+    def fast_phases(self, enable=True):
+        """Measurement (extend="fast" on the device): the device-event times in ms of the last extend's phases,
+        as a dict, recorded while enabled; `enable` switches the recording for the next calls."""
+        ms = np.zeros(6, np.float64)
+        check(lib().gs_unsup_fast_phases(self._h, int(bool(enable)), ptr(ms)))
+        return dict(zip(("walks", "balls", "masks", "negatives", "unique", "copy_back"), ms.tolist()))
 
     def __del__(self):
         h = getattr(self, "_h", None)

@@ -340,6 +340,31 @@ int gs_unsup_attach_device(gs_unsup* u, void* stream);
 int gs_unsup_extend(gs_unsup* u, gs_rng* rng, const int64_t* nodes, int64_t n,
                     int64_t num_neg, int32_t parts, int32_t n_threads,
                     int64_t* sizes);
+/* extend_nodes without CPython parity: a pure function of
+ * (graph, train set, seed, batch_index, nodes, num_neg, the walk constants,
+ * parts).  No rng: the random word of draw t of the node at position r is
+ * draw_word(seed, batch_index, r, tag, t) of the counter-based sampler
+ * (Philox4x32-10), tag 0xF0 for the walks (t = walk * walk_len + step) and
+ * 0xF1 for the negatives.  A walk step goes to row[randbelow(deg, word)]; a
+ * walk that reaches an empty row stops.  The far list of a node is the
+ * distinct train ids outside its n_walk_len-hop ball in ascending order; the
+ * negatives are the whole list when num_neg >= its length, else Floyd's
+ * algorithm's num_neg picks in draw order.  unique_nodes_batch is the distinct
+ * pair members in ascending order.  parts, sizes and the members
+ * gs_unsup_fetch / gs_unsup_loss_plan read are those of gs_unsup_extend.
+ * With a device attached (gs_unsup_attach_device) the whole call runs on the
+ * device half's stream, two host synchronisations; otherwise the sequential
+ * host mirror runs (balls on n_threads threads).  Both give the same bits.
+ * GS_EINVAL: num_neg > 1024, n_walks * walk_len > 65536; GS_ERANGE:
+ * num_neg < 0, an id outside the graph. */
+int gs_unsup_extend_fast(gs_unsup* u, uint64_t seed, int64_t batch_index,
+                         const int64_t* nodes, int64_t n, int64_t num_neg,
+                         int32_t parts, int32_t n_threads, int64_t* sizes);
+/* Measurement: ms[6] (NULL skips) receives the device-event times of the last
+ * device gs_unsup_extend_fast's phases — walks, balls, masks, negatives,
+ * unique, copy-back — recorded while enabled; enable != 0 makes the next calls
+ * record them.  GS_EINVAL without a device. */
+int gs_unsup_fast_phases(gs_unsup* u, int32_t enable, double* ms);
 /* Copy out the last extend: unique[sizes0], pos_pairs[2*sizes1] and
  * neg_pairs[2*sizes2] as (node, other) in append order, per input node its
  * positive / negative pair counts and has_pos (node is a key of
