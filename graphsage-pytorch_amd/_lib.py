@@ -115,6 +115,11 @@ _SIGS = {
     "gs_cls_nll_ws_floats": (_i64, [_i64, _i64, _i64]),
     "gs_cls_nll_fwd_bwd": (_i32, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
                                   _vp, _vp, _vp]),
+    "gs_cls_probe_supported": (_i32, [_i64, _i64, _i64]),
+    "gs_cls_probe_run": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _f32, _f32, _vp, _vp,
+                                _vp]),
+    "gs_cls_probe_run_ex": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _f32, _f32, _vp,
+                                   _vp, _i64, _vp]),
     "gs_clip_sgd": (_i32, [_i32, _vp, _vp, _vp, _f32, _f32, _f32, _vp, _vp]),
     "gs_clip_adam": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i64, _vp,
                             _vp]),

@@ -651,6 +651,94 @@ def cls_nll_fwd_bwd(E, Wc, bc, labels, loss, dE, dWc, dbc, ws, roots=None, mask_
                                    ptr(dE), ptr(dWc), ptr(dbc), ptr(ws), _stream(E)))
 
 
+def cls_probe_supported(D, C, batch):
+    """gs_cls_probe_supported: the probe kernel's LDS image fits (no device work)."""
+    return bool(lib().gs_cls_probe_supported(int(D), int(C), int(batch)))
+
+
+def cls_probe(E, labels, order, params, batch, lr, max_norm, snapshots=None, losses=None, *,
+              max_steps_per_launch=0):
+    """train_classification's loop over frozen embeddings (gs_cls_probe_run):
+    E [N, D] fp32 with unit column stride, labels [N] int32, order
+    [n_epochs, n_train] int32 row ids, params [C*D + C] (W row-major then b,
+    updated in place), snapshots [n_epochs, C*D + C] and losses
+    [n_epochs, steps] optional.  Ids and labels are not checked here
+    (train.ClassifierProbe does).  max_steps_per_launch: a smaller launch cut
+    than the library's (the result does not depend on it)."""
+    _dev(E, labels, order, params, snapshots, losses)
+    if E.dtype != torch.float32 or E.dim() != 2 or E.stride(1) != 1:
+        raise ValueError("embeddings must be float32 [N, D] with unit column stride")
+    if _i32(order).dim() != 2 or not order.is_contiguous():
+        raise ValueError("order must be a contiguous int32 [n_epochs, n_train]")
+    if _i32(labels).dim() != 1 or not labels.is_contiguous() or labels.numel() != E.shape[0]:
+        raise ValueError("labels must be a contiguous int32 [N]")
+    N, D = E.shape
+    n_epochs, n_train = order.shape
+    P = params.numel()
+    if params.dtype != torch.float32 or not params.is_contiguous() or P % (D + 1) != 0 or P == 0:
+        raise ValueError("params must be a contiguous float32 [C*D + C]")
+    C = P // (D + 1)
+    steps = -(-n_train // int(batch)) if int(batch) >= 1 else 0
+    for t, shape, what in ((snapshots, n_epochs * P, "snapshots [n_epochs, C*D + C]"),
+                           (losses, n_epochs * steps, "losses [n_epochs, steps]")):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != shape):
+            raise ValueError(f"{what} must be contiguous float32")
+    check(lib().gs_cls_probe_run_ex(ptr(E), E.stride(0), N, D, C, ptr(labels), ptr(order), n_train, int(batch),
+                                    n_epochs, ptr(params), float(lr), float(max_norm), ptr(snapshots), ptr(losses),
+                                    int(max_steps_per_launch), _stream(E)))
+    return params
+
+
+def cls_probe_host(E, labels, order, params, batch, lr, max_norm, dtype=None):
+    """cls_probe in plain numpy, its CPU reference (as full_field_host is of
+    full_field): the same step in `dtype` (float64 by default) with numpy's own
+    summation order.  Nothing is modified; returns (params, snapshots
+    [n_epochs, P], losses [n_epochs, steps])."""
+    import numpy as np
+    dt = np.dtype(np.float64 if dtype is None else dtype).type
+    E = np.asarray(E, dt)
+    labels = np.asarray(labels, np.int64).reshape(-1)
+    order = np.asarray(order, np.int64)
+    if E.ndim != 2 or order.ndim != 2 or len(labels) != len(E):
+        raise ValueError("cls_probe_host: E [N, D], labels [N], order [n_epochs, n_train]")
+    if order.size and (order.min() < 0 or order.max() >= len(E)):
+        raise IndexError("cls_probe_host: row id out of range")
+    N, D = E.shape
+    p = np.array(params, dt).reshape(-1)
+    if p.size == 0 or p.size % (D + 1):
+        raise ValueError("cls_probe_host: params must hold C*D + C values")
+    C = p.size // (D + 1)
+    batch = int(batch)
+    if batch < 1 or order.shape[0] < 1 or order.shape[1] < 1:
+        raise ValueError("cls_probe_host: batch, n_epochs and n_train must be >= 1")
+    n_epochs, n_train = order.shape
+    steps = -(-n_train // batch)
+    lr, max_norm, eps = dt(lr), dt(max_norm), dt(1e-6)
+    W, b = p[:C * D].reshape(C, D), p[C * D:]
+    snaps = np.empty((n_epochs, p.size), dt)
+    losses = np.empty((n_epochs, steps), dt)
+    for e in range(n_epochs):
+        for s in range(steps):
+            rows = order[e, s * batch:(s + 1) * batch]
+            n = len(rows)
+            X, y = E[rows], labels[rows]
+            z = X @ W.T + b
+            z = z - z.max(1, keepdims=True)
+            logp = z - np.log(np.exp(z).sum(1, keepdims=True))
+            has = (y >= 0) & (y < C)  # outside [0, C): no class
+            losses[e, s] = -logp[np.nonzero(has)[0], y[has]].sum() / dt(n)
+            G = np.exp(logp)
+            G[np.nonzero(has)[0], y[has]] -= dt(1)
+            G = G / dt(n)
+            dW, db = G.T @ X, G.sum(0)
+            norm = np.sqrt((dW * dW).sum() + (db * db).sum())
+            coef = min(dt(1), max_norm / (norm + eps))
+            W -= lr * (dW * coef)  # views of p
+            b -= lr * (db * coef)
+        snaps[e] = p
+    return p.copy(), snaps, losses
+
+
 def unsup_loss_workspace(M, P, N, device):
     """The buffer unsup_loss_fwd leaves for unsup_loss_bwd: {coef, cos, n1, n2} per pair (the P positive
     pairs, then the N negative ones), then the M node scores at float offset 4 (P + N)."""

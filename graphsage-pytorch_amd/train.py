@@ -1115,3 +1115,109 @@ class FullTrainer:
         for dst, src in zip(self._embedder.W, self.weights()):
             dst.copy_(src)
         return self._embedder.embed(nodes)
+
+
+class ClassifierProbe:
+    """The linear probe of train_classification (utils.py:80-111) on frozen
+    embeddings: every batch-`batch` SGD step of every epoch inside the
+    persistent single-workgroup kernel (hip_ops.cls_probe), with one
+    clip_grad_norm_(max_norm) over weight and bias together and SGD(lr).
+    Parameters are named as Classification names them (layer.0.weight [C, D],
+    layer.0.bias [C]) and live in one flat buffer, W row-major then b.
+    `weights`: (W, b), or None for the reference's initialisation of
+    Classification(D, n_classes) under torch.manual_seed(seed).
+
+    Everything is validated here, once (ValueError): labels in [0, n_classes),
+    `embeddings` fp32 2-D with unit column stride on a HIP device, and a shape
+    the kernel supports (gs_cls_probe_supported).  There is no other path."""
+
+    def __init__(self, embeddings, labels, n_classes, weights=None, lr=0.5, max_norm=5.0, batch=50, seed=824):
+        E = embeddings
+        if not isinstance(E, torch.Tensor) or not E.is_cuda:
+            raise ValueError("ClassifierProbe: embeddings must be a tensor on a HIP device")
+        if E.dtype != torch.float32 or E.dim() != 2 or E.stride(1) != 1 or E.shape[0] < 1 or E.shape[1] < 1:
+            raise ValueError("ClassifierProbe: embeddings must be float32 [N, D] with unit column stride")
+        self.E = E.detach()
+        self.device = E.device
+        self.N, self.D = int(E.shape[0]), int(E.shape[1])
+        self.C, self.batch = int(n_classes), int(batch)
+        self.lr, self.max_norm = float(lr), float(max_norm)
+        if self.C < 1 or self.batch < 1:
+            raise ValueError("ClassifierProbe: n_classes and batch must be >= 1")
+        if not ops.cls_probe_supported(self.D, self.C, self.batch):
+            raise ValueError(f"ClassifierProbe: (D, C, batch) = ({self.D}, {self.C}, {self.batch}) does not fit "
+                             "the probe kernel's LDS (gs_cls_probe_supported)")
+        y = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels).reshape(-1)
+        if len(y) != self.N or not np.issubdtype(y.dtype, np.integer):
+            raise ValueError("ClassifierProbe: labels must be N integers")
+        if y.min() < 0 or y.max() >= self.C:
+            raise ValueError("ClassifierProbe: labels must lie in [0, n_classes)")
+        self.labels = torch.from_numpy(y.astype(np.int32)).to(self.device)
+        if weights is None:
+            torch.manual_seed(seed)
+            lin = Classification(self.D, self.C).layer[0]
+            weights = (lin.weight.detach(), lin.bias.detach())
+        W, b = weights
+        if tuple(W.shape) != (self.C, self.D) or tuple(b.shape) != (self.C,):
+            raise ValueError(f"ClassifierProbe: weights must be ([{self.C}, {self.D}], [{self.C}])")
+        self.p = FlatParams([W, b], ["layer.0.weight", "layer.0.bias"], [0], self.device)
+
+    def state_dict(self):
+        return self.p.state_dict()
+
+    def load_state_dict(self, sd):
+        """Copy the named parameters of state_dict() (or of a Classification) into the flat buffer."""
+        for i, n in enumerate(self.p.names):
+            self.p.view(i).copy_(sd[n])
+
+    def weights(self):
+        """Views of the flat buffer: (layer.0.weight, layer.0.bias)."""
+        return self.p.view(0), self.p.view(1)
+
+    def steps_per_epoch(self, n_train):
+        return -(-int(n_train) // self.batch)
+
+    def _order(self, order):
+        """`order` as a device int32 [n_epochs, n_train], its ids checked against [0, N): on the host for an array
+        or a CPU tensor; a device tensor is checked on the device, which waits for it."""
+        if isinstance(order, torch.Tensor) and order.is_cuda:
+            if order.dim() != 2 or order.numel() == 0 or order.dtype not in (torch.int32, torch.int64):
+                raise ValueError("ClassifierProbe.run: order must be an integer [n_epochs, n_train]")
+            if bool(((order < 0) | (order >= self.N)).any()):
+                raise IndexError("ClassifierProbe.run: row id out of range")
+            return order.to(device=self.device, dtype=torch.int32).contiguous()
+        o = np.asarray(order.numpy() if isinstance(order, torch.Tensor) else order)
+        if o.ndim != 2 or o.size == 0 or not np.issubdtype(o.dtype, np.integer):
+            raise ValueError("ClassifierProbe.run: order must be an integer [n_epochs, n_train]")
+        if o.min() < 0 or o.max() >= self.N:
+            raise IndexError("ClassifierProbe.run: row id out of range")
+        return torch.from_numpy(np.ascontiguousarray(o, dtype=np.int32)).to(self.device)
+
+    def run(self, order, *, max_steps_per_launch=0):
+        """Train over order [n_epochs, n_train] (row e: epoch e's shuffled
+        ids, batches in that order).  Returns (losses [n_epochs, steps],
+        snapshots [n_epochs, P]) on the device: every step's loss and the flat
+        parameters after each epoch; the parameters themselves end in this
+        object.  Nothing here waits for the device."""
+        o = self._order(order)
+        n_epochs, n_train = o.shape
+        P = self.p.params.numel()
+        losses = torch.empty(n_epochs, self.steps_per_epoch(n_train), dtype=torch.float32, device=self.device)
+        snaps = torch.empty(n_epochs, P, dtype=torch.float32, device=self.device)
+        ops.cls_probe(self.E, self.labels, o, self.p.params, self.batch, self.lr, self.max_norm, snaps, losses,
+                      max_steps_per_launch=max_steps_per_launch)
+        return losses, snaps
+
+    def predict(self, nodes, snapshots=None):
+        """argmax class of the frozen rows `nodes` under the current
+        parameters ([n]), or under every row of `snapshots` at once
+        ([n_epochs, n]: one batched torch.matmul)."""
+        ids = torch.as_tensor(np.asarray(nodes), device=self.device).long()
+        X = self.E.index_select(0, ids)
+        C, D = self.C, self.D
+        if snapshots is None:
+            W, b = self.weights()
+            return (X @ W.t() + b).argmax(1)
+        S = snapshots.reshape(-1, C * D + C)
+        W = S[:, :C * D].reshape(-1, C, D)
+        return (torch.matmul(X, W.transpose(1, 2)) + S[:, None, C * D:]).argmax(2)

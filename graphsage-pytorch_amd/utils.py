@@ -308,10 +308,107 @@ def evaluate(dataCenter, ds, graphSage, classification, device, max_vali_f1, nam
     return max_vali_f1
 
 
-def train_classification(dataCenter, graphSage, classification, ds, device, max_vali_f1, name, epochs=800):
+def micro_f1(labels, predicts):
+    """Micro-averaged F1 of single-label multi-class predictions, which is the
+    accuracy: every wrong prediction is one false positive (its class) and one
+    false negative (the true class), so precision = recall = correct / n.
+    sklearn's f1_score(average="micro") computes 2·p·r / (p + r) from them, which
+    rounds its product and its quotient: the two values are equal up to those
+    two roundings (2 ulp), not always bit for bit."""
+    labels, predicts = np.asarray(labels), np.asarray(predicts)
+    return float((labels == predicts).sum()) / float(labels.shape[-1])
+
+
+def _set_classifier(classification, flat):
+    """The flat probe parameters (W row-major, then b) into classification's own Parameters."""
+    lin = classification.layer[0]
+    nw = lin.weight.numel()
+    with torch.no_grad():
+        lin.weight.copy_(flat[:nw].view_as(lin.weight))
+        lin.bias.copy_(flat[nw:].view_as(lin.bias))
+
+
+def _train_classification_native(dataCenter, graphSage, classification, ds, device, max_vali_f1, name, epochs,
+                                 evaluate_on):
+    """train_classification's native path: every epoch's shuffle drawn up
+    front, the whole run in train.ClassifierProbe, then the evaluation."""
+    from sklearn.utils import shuffle
+    from .train import ClassifierProbe
+    print("Training Classification ...")
+    b_sz = 50
+    train_nodes = getattr(dataCenter, ds + "_train")
+    labels = getattr(dataCenter, ds + "_labels")
+    features = get_gnn_embeddings(graphSage, dataCenter, ds)
+    if epochs < 1:  # the loop's range(epochs) is empty: nothing after the embeddings
+        return classification, max_vali_f1
+    lin = classification.layer[0]
+    probe = ClassifierProbe(features, labels, lin.out_features, weights=(lin.weight.detach(), lin.bias.detach()),
+                            lr=0.5, max_norm=5.0, batch=b_sz)
+    order = []
+    for epoch in range(epochs):  # chained as the loop chains them: numpy's stream ends where the loop leaves it
+        train_nodes = shuffle(train_nodes)
+        order.append(np.asarray(train_nodes))
+    _, snapshots = probe.run(np.stack(order))
+    if evaluate_on == "model":
+        for epoch in range(epochs):
+            _set_classifier(classification, snapshots[epoch])
+            max_vali_f1 = evaluate(dataCenter, ds, graphSage, classification, device, max_vali_f1, name, epoch)
+        return classification, max_vali_f1
+
+    test_nodes = getattr(dataCenter, ds + "_test")
+    val_nodes = getattr(dataCenter, ds + "_val")
+    val_pred = probe.predict(val_nodes, snapshots).cpu().numpy()    # [epochs, n_val]
+    test_pred = probe.predict(test_nodes, snapshots).cpu().numpy()
+    labels_val, labels_test = np.asarray(labels)[val_nodes], np.asarray(labels)[test_nodes]
+    models = [graphSage, classification]
+    for epoch in range(epochs):
+        vali_f1 = micro_f1(labels_val, val_pred[epoch])
+        print("Validation F1:", vali_f1)
+        if vali_f1 > max_vali_f1:
+            max_vali_f1 = vali_f1
+            test_f1 = micro_f1(labels_test, test_pred[epoch])
+            print("Test F1:", test_f1)
+            _set_classifier(classification, snapshots[epoch])
+            os.makedirs("models", exist_ok=True)
+            torch.save(models, "models/model_best_{}_ep{}_{:.4f}.torch".format(name, epoch, test_f1))
+    _set_classifier(classification, snapshots[epochs - 1])
+    return classification, max_vali_f1
+
+
+def train_classification(dataCenter, graphSage, classification, ds, device, max_vali_f1, name, epochs=800,
+                         native=False, evaluate_on="model"):
     """Classifier on frozen embeddings (utils.py:80-111): get_gnn_embeddings,
     then per epoch sklearn-shuffled batches of 50, -Σ logp[label] / n through
-    the fused HIP head, clip_grad_norm_(5), SGD(lr=0.5), evaluate()."""
+    the fused HIP head, clip_grad_norm_(5), SGD(lr=0.5), evaluate().
+
+    `native=True`: the same run through train.ClassifierProbe.  Every epoch's
+    shuffle is drawn up front (numpy's global stream has no other consumer in
+    the loop, so it ends in the same state), all epochs' steps run in whole
+    launches of one persistent kernel, then for each epoch in order its
+    parameters are copied into `classification` and evaluate() is called
+    exactly as the loop calls it: Python's `random` stream, the prints, the
+    checkpoints and the return value are the loop's; only the fp32 summation
+    order of a step differs.  A shape the kernel does not support raises
+    ValueError; there is no fallback to the loop.
+
+    `evaluate_on="frozen"` (with native=True only; ValueError otherwise) is
+    NOT the reference's evaluation, which calls GraphSage on the validation
+    (and test) nodes after every epoch and so re-samples their neighbourhoods
+    each time.  Here the validation and test predictions of all epochs come
+    from the frozen embeddings the classifier was trained on
+    (ClassifierProbe.predict), micro-F1 is computed as accuracy (micro_f1:
+    equal to sklearn's value up to sklearn's own rounding, so an F1 print or
+    a checkpoint name can differ from evaluate's formatting in the last bit),
+    and the epochs are walked in order: test F1, checkpoint and "Test F1"
+    print only when validation improves, as evaluate does.  No `random` draw
+    and no GraphSage forward after the embeddings."""
+    if evaluate_on not in ("model", "frozen"):
+        raise ValueError(f"evaluate_on must be 'model' or 'frozen', got {evaluate_on!r}")
+    if evaluate_on == "frozen" and not native:
+        raise ValueError("evaluate_on='frozen' needs native=True")
+    if native:
+        return _train_classification_native(dataCenter, graphSage, classification, ds, device, max_vali_f1, name,
+                                            epochs, evaluate_on)
     from sklearn.utils import shuffle
     print("Training Classification ...")
     c_optimizer = torch.optim.SGD(classification.parameters(), lr=0.5)

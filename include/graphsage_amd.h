@@ -536,6 +536,50 @@ int gs_clip_adam(int32_t n_groups, const int64_t* goff_host, float* params,
                  float lr, float beta1, float beta2, float eps, float weight_decay,
                  int64_t step, float* ws, void* stream);
 
+/* train_classification's loop (utils.py:89-108) over frozen embeddings, every
+ * step of every epoch in launches of one persistent workgroup (the parameters,
+ * the batch's rows and the step's scratch live in LDS; the next batch's rows
+ * are fetched while the current one is computed).
+ *   E        [n_rows, D] fp32 rows with stride lde (device), never written
+ *   labels   [n_rows] int32 (device); a label outside [0, C) is "no class": its
+ *            row contributes the softmax term only
+ *   order    [n_epochs * n_train] int32 row ids (device): step s of epoch e
+ *            covers order[e*n_train + s*batch ...]; the last batch of an epoch
+ *            has n = n_train - s*batch rows and its mean is over n.  Ids are
+ *            not checked on the device: the caller guarantees [0, n_rows)
+ *   params   [C*D + C]: W row-major then b (device), read at the start and
+ *            written at the end
+ *   snapshots NULL or [n_epochs, C*D + C]: the parameters after each epoch
+ *   losses   NULL or [n_epochs * ceil(n_train / batch)]: every step's loss
+ * One step: logits = E[rows]·Wᵀ + b, max-shifted log_softmax,
+ * loss = -Σ logp[i, y_i] / n, G = (softmax - onehot) / n, dW = Gᵀ·E[rows],
+ * db = Σ_i G[i], one clip over W and b together (coef = min(1, max_norm /
+ * (‖g‖ + 1e-6)); max_norm = INFINITY: none), p = fma(-lr, g·coef, p).
+ * Deterministic: every sum in an order fixed by the shape, no atomics.
+ * The run is cut into launches of at most 65,536 steps; the _ex form takes a
+ * smaller cut (max_steps_per_launch >= 1; <= 0: the default).  The result does
+ * not depend on the cut, bit for bit.
+ * gs_cls_probe_supported (1 / 0, no device work): the LDS image fits the
+ * 160 KiB of one workgroup.  In floats, with round4(x) = x rounded up to a
+ * multiple of 4, LD = D + 4 where D % 4 == 0 and D | 1 otherwise:
+ *   2·round4(C·D + C) + round4(batch·LD) + round4(batch·(C | 1))
+ *     + 4·round4(batch) + 32  <=  40960
+ * and batch <= 512 (the workgroup's threads: one carries each row's id and
+ * label between steps).
+ * GS_EINVAL (before any device work): a NULL E / labels / order / params, a
+ * size < 1, lde < D, lr not finite, max_norm <= 0 or NaN, an unsupported
+ * shape. */
+int gs_cls_probe_supported(int64_t D, int64_t C, int64_t batch);
+int gs_cls_probe_run(const float* E, int64_t lde, int64_t n_rows, int64_t D, int64_t C,
+                     const int32_t* labels, const int32_t* order, int64_t n_train,
+                     int64_t batch, int64_t n_epochs, float* params, float lr,
+                     float max_norm, float* snapshots, float* losses, void* stream);
+int gs_cls_probe_run_ex(const float* E, int64_t lde, int64_t n_rows, int64_t D, int64_t C,
+                        const int32_t* labels, const int32_t* order, int64_t n_train,
+                        int64_t batch, int64_t n_epochs, float* params, float lr,
+                        float max_norm, float* snapshots, float* losses,
+                        int64_t max_steps_per_launch, void* stream);
+
 /* f32 → bf16 (RNE) cast, n elements. */
 int gs_cast_f32_bf16(const float* in, void* out, int64_t n, void* stream);
 
