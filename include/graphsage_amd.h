@@ -721,7 +721,10 @@ int gs_trainer_defer(gs_trainer* t, int32_t on, int32_t* active, void* stream);
  * loop; all default 1).  Each alternative
  * exists for the tests that compare it with the default.  fused_bwd, self_rows and defer_update compute bitwise the
  * default's results; top_launch matches them within fp32 rounding of the
- * k order (its split-K partial sums are added in a fixed, different order):
+ * k order (its split-K partial sums are added in a fixed, different order);
+ * the top launch needs the fused backward, so where it runs (two layers,
+ * hidden 128, at most 32 classes, no gcn) fused_bwd 0 turns it off as well
+ * and matches the default within that rounding, not bitwise:
  *   GS_TOPT_FUSED_BWD     1: layers >= 2 backward in fused launches
  *   GS_TOPT_TOP_LAUNCH    1: a 2-layer step's layer 2 + loss head + dIn2 in one launch
  *   GS_TOPT_SELF_ROWS     1: gather slots hold [self | agg] rows (next gs_trainer_gather_reserve)

@@ -64,10 +64,12 @@ def _dev(roots):
     return torch.from_numpy(roots.astype(np.int32)).to(DEV)
 
 
-@pytest.mark.parametrize("case_id", sc.IDS)
-def test_step_matches_float64_reference(gs, case_id):
-    """(a): two teacher-forced steps of the row against the float64 reference."""
-    case = sc.BY_ID[case_id]
+def check_step_against_float64(case, defers, factor=sc.factor, figures=None):
+    """Two teacher-forced steps of the row `case` against the float64
+    reference; `defers`: whether trainer_defer_update takes effect for it;
+    `factor(case id, tensor name)`: check_rule's factor; `figures`: a list
+    that takes check_rule's figures."""
+    case_id = case["id"]
     wl = _workload(case)
     L, F, H, C, B = case["L"], case["F"], case["H"], case["C"], case["B"]
     offs = step_ref.param_offsets(L, F, H, C, case["gcn"])
@@ -99,7 +101,7 @@ def test_step_matches_float64_reference(gs, case_id):
 
         def rule(name, got, ref, tor):
             check_rule(f"{tag} {name}", got, np.asarray(ref).reshape(-1), np.asarray(tor).reshape(-1),
-                       factor=sc.factor(case_id, name))
+                       figures=figures, factor=factor(case_id, name))
 
         rule("emb_fwd", out.cpu().numpy(), e64, e32)
         rule("emb", emb_cap[0].cpu().numpy(), e64, e32)
@@ -118,8 +120,14 @@ def test_step_matches_float64_reference(gs, case_id):
         p32, gc32 = step_ref.clip_sgd_torch_fp32(before, graw, goff, lr, max_norm)
         rule("params", tr.p.params.cpu().numpy(), p64, p32)
         rule("clipped", tr.p.grads.cpu().numpy(), gc64, gc32)
-    assert trs[1].defer(True) is (case_id in DEFERS)
+    assert trs[1].defer(True) is defers
     trs[1].defer(False)
+
+
+@pytest.mark.parametrize("case_id", sc.IDS)
+def test_step_matches_float64_reference(gs, case_id):
+    """(a): two teacher-forced steps of the row against the float64 reference."""
+    check_step_against_float64(sc.BY_ID[case_id], case_id in DEFERS)
 
 
 @pytest.mark.parametrize("case_id", ["h64", "h80", "h256", "l3", "l3m", "slabs"])
