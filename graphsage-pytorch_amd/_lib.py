@@ -120,6 +120,10 @@ _SIGS = {
                                 _vp]),
     "gs_cls_probe_run_ex": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _f32, _f32, _vp,
                                    _vp, _i64, _vp]),
+    "gs_cls_eval_wc_lds_floats": (_i64, []),
+    "gs_cls_eval_ws_bytes": (_i64, [_i64, _i64, _i64, _i64]),
+    "gs_cls_eval": (_i32, [_i64, _i64, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp,
+                           _i64, _vp]),
     "gs_clip_sgd": (_i32, [_i32, _vp, _vp, _vp, _f32, _f32, _f32, _vp, _vp]),
     "gs_clip_adam": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i64, _vp,
                             _vp]),

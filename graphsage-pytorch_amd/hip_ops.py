@@ -739,6 +739,104 @@ def cls_probe_host(E, labels, order, params, batch, lr, max_norm, dtype=None):
     return p.copy(), snaps, losses
 
 
+def cls_eval(H, labels, params, C, rows=None, labels_by_row=True, n_sets=1, set_stride=None, want_pred=True,
+             want_logp=False):
+    """The classifier head forward only (gs_cls_eval): log_softmax(H[rows]·Wcᵀ
+    + bc), its argmax (the lowest index among the maxima), the mean NLL and the
+    confusion matrix, for n_sets parameter sets at once.
+
+    H [*, D] fp32 with unit column stride; rows: None (every row of H) or [B]
+    int32 ids into H (not checked here: the caller guarantees them); labels
+    int32, row i's label labels[rows[i]] (labels_by_row, with rows) or
+    labels[i]; params: a contiguous fp32 vector whose set s starts at
+    s·set_stride (default C·D + C) and holds Wc [C, D] row-major, then bc [C].
+    A label outside [0, C) leaves its row out of the loss and the matrix and
+    counts it in n_bad.  Returns (loss [n_sets], counts [n_sets, C·C + 2] int64
+    -- counts[y·C + pred], then n_counted and n_bad --, pred [n_sets, B] int32
+    or None, logp [n_sets, B, C] or None) on the device; nothing here waits
+    for the device."""
+    _dev(H, labels, params, rows)
+    if H.dtype != torch.float32 or H.dim() != 2 or H.stride(1) != 1 or H.shape[0] < 1 or H.shape[1] < 1:
+        raise ValueError("H must be float32 [N, D] with unit column stride")
+    D, C, n_sets = int(H.shape[1]), int(C), int(n_sets)
+    if C < 1 or n_sets < 1:
+        raise ValueError("C and n_sets must be >= 1")
+    if rows is not None and (_i32(rows).dim() != 1 or not rows.is_contiguous() or rows.numel() < 1):
+        raise ValueError("rows must be a contiguous int32 vector of at least one id")
+    B = int(H.shape[0] if rows is None else rows.numel())
+    by_row = bool(labels_by_row) and rows is not None
+    if _i32(labels).dim() != 1 or not labels.is_contiguous() or labels.numel() < (H.shape[0] if by_row else B):
+        raise ValueError("labels must be a contiguous int32 vector, one per row of H (labels_by_row) or per "
+                         "evaluated row")
+    stride = C * D + C if set_stride is None else int(set_stride)
+    if params.dtype != torch.float32 or params.dim() != 1 or not params.is_contiguous():
+        raise ValueError("params must be a contiguous float32 vector")
+    if stride < C * D + C or params.numel() < (n_sets - 1) * stride + C * D + C:
+        raise ValueError("params must hold n_sets sets of C*D + C values, set_stride >= C*D + C apart")
+    dev = H.device
+    need = int(lib().gs_cls_eval_ws_bytes(B, D, C, n_sets))
+    if need < 0:
+        check(_lib.GS_EINVAL)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    loss = torch.empty(n_sets, dtype=torch.float32, device=dev)
+    counts = torch.empty(n_sets, C * C + 2, dtype=torch.int64, device=dev)
+    pred = torch.empty(n_sets, B, dtype=torch.int32, device=dev) if want_pred else None
+    logp = torch.empty(n_sets, B, C, dtype=torch.float32, device=dev) if want_logp else None
+    check(lib().gs_cls_eval(B, D, C, ptr(H), H.stride(0), ptr(rows), ptr(labels), int(by_row), ptr(params), n_sets,
+                            stride, ptr(pred), ptr(logp), ptr(loss), ptr(counts), ptr(ws), need, _stream(H)))
+    return loss, counts, pred, logp
+
+
+def cls_eval_host(H, labels, params, C, rows=None, labels_by_row=True, n_sets=1, set_stride=None, dtype=None):
+    """cls_eval in plain numpy, its CPU reference: the same function in
+    `dtype` (float64 by default) with numpy's own summation order, the same tie
+    rule (np.argmax: the lowest index among the maxima, a NaN is maximal and
+    the first NaN wins) and the same bad-label rule.  Returns (loss [n_sets],
+    counts [n_sets, C·C + 2] int64, pred [n_sets, B] int32, logp
+    [n_sets, B, C])."""
+    import numpy as np
+    dt = np.dtype(np.float64 if dtype is None else dtype).type
+    H = np.asarray(H)
+    if H.ndim != 2 or H.shape[0] < 1 or H.shape[1] < 1:
+        raise ValueError("cls_eval_host: H [N, D]")
+    D, C, n_sets = H.shape[1], int(C), int(n_sets)
+    if C < 1 or n_sets < 1:
+        raise ValueError("cls_eval_host: C and n_sets must be >= 1")
+    labels = np.asarray(labels, np.int64).reshape(-1)
+    if rows is None:
+        X, y = H.astype(dt), labels[:H.shape[0]]
+    else:
+        rows = np.asarray(rows, np.int64).reshape(-1)
+        if rows.size < 1 or rows.min() < 0 or rows.max() >= H.shape[0]:
+            raise IndexError("cls_eval_host: row id out of range")
+        X, y = H[rows].astype(dt), labels[rows] if labels_by_row else labels[:rows.size]
+    B = X.shape[0]
+    if len(y) != B:
+        raise ValueError("cls_eval_host: too few labels")
+    stride = C * D + C if set_stride is None else int(set_stride)
+    p = np.asarray(params).reshape(-1)
+    if stride < C * D + C or p.size < (n_sets - 1) * stride + C * D + C:
+        raise ValueError("cls_eval_host: params must hold n_sets sets of C*D + C values")
+    has = (y >= 0) & (y < C)  # outside [0, C): not counted
+    idx, yh = np.nonzero(has)[0], y[has]
+    loss = np.empty(n_sets, dt)
+    counts = np.zeros((n_sets, C * C + 2), np.int64)
+    pred = np.empty((n_sets, B), np.int32)
+    logp = np.empty((n_sets, B, C), dt)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for s in range(n_sets):
+            W = p[s * stride:s * stride + C * D].reshape(C, D).astype(dt)
+            b = p[s * stride + C * D:s * stride + C * D + C].astype(dt)
+            z = X @ W.T + b
+            pred[s] = np.argmax(z, 1)
+            zs = z - z.max(1, keepdims=True)
+            logp[s] = zs - np.log(np.exp(zs).sum(1, keepdims=True))
+            loss[s] = -logp[s][idx, yh].sum(dtype=dt) / dt(len(idx)) if len(idx) else dt(np.nan)
+            counts[s, :C * C] = np.bincount(yh * C + pred[s][has], minlength=C * C)
+            counts[s, C * C], counts[s, C * C + 1] = len(idx), B - len(idx)
+    return loss, counts, pred, logp
+
+
 def unsup_loss_workspace(M, P, N, device):
     """The buffer unsup_loss_fwd leaves for unsup_loss_bwd: {coef, cos, n1, n2} per pair (the P positive
     pairs, then the N negative ones), then the M node scores at float offset 4 (P + N)."""

@@ -708,6 +708,59 @@ class UnsupBatch:
         return self.uws[off:off + 4 * U * hidden].view(torch.float32).view(U, hidden)
 
 
+class EvalResult:
+    """What hip_ops.cls_eval left on the device -- `loss` (the mean NLL over
+    the counted rows), `counts` ([C·C + 2] int64: the confusion matrix, then
+    n_counted and n_bad), `pred` ([B] int32) and `logp` ([B, C], or None) --
+    and the metrics of the confusion matrix, computed on first use in float64
+    from one download of `counts`:
+
+        confusion [C, C] int64 (row = true class), n, n_bad,
+        accuracy, micro_f1 (equal to the accuracy: utils.micro_f1's docstring),
+        macro_f1 (the plain mean over all C classes),
+        per_class: {"precision", "recall", "f1", "support"} arrays of C.
+
+    A class with no true and no predicted row scores 0 (sklearn's
+    zero_division=0); with no counted row the accuracy is NaN.  A result over
+    several parameter sets (ClassifierProbe.evaluate with snapshots) carries a
+    leading dimension on every tensor and every metric."""
+
+    def __init__(self, loss, counts, pred, logp):
+        self.loss, self.counts, self.pred, self.logp = loss, counts, pred, logp
+        self._m = None
+
+    def _metrics(self):
+        if self._m is None:
+            c = self.counts.cpu().numpy().astype(np.int64)   # the one download
+            C = int(round(np.sqrt(c.shape[-1] - 2)))
+            lead = c.shape[:-1]
+            conf = c[..., :C * C].reshape(lead + (C, C))
+            n, n_bad = c[..., C * C], c[..., C * C + 1]
+            tp = np.diagonal(conf, axis1=-2, axis2=-1).astype(np.float64)
+            support, predicted = conf.sum(-1), conf.sum(-2)
+
+            def ratio(num, den):
+                den = np.asarray(den, np.float64)
+                return np.divide(num, den, out=np.zeros_like(den), where=den > 0)
+
+            acc = np.divide(tp.sum(-1), n, out=np.full(lead, np.nan), where=n > 0)
+            f1 = ratio(2.0 * tp, support + predicted)
+            scalar = (lambda x: x.item()) if not lead else (lambda x: x)
+            self._m = {"confusion": conf, "n": scalar(n), "n_bad": scalar(n_bad), "accuracy": scalar(acc),
+                       "macro_f1": scalar(f1.mean(-1)),
+                       "per_class": {"precision": ratio(tp, predicted), "recall": ratio(tp, support), "f1": f1,
+                                     "support": support}}
+        return self._m
+
+    confusion = property(lambda self: self._metrics()["confusion"])
+    n = property(lambda self: self._metrics()["n"])
+    n_bad = property(lambda self: self._metrics()["n_bad"])
+    accuracy = property(lambda self: self._metrics()["accuracy"])
+    micro_f1 = property(lambda self: self._metrics()["accuracy"])
+    macro_f1 = property(lambda self: self._metrics()["macro_f1"])
+    per_class = property(lambda self: self._metrics()["per_class"])
+
+
 class FullTrainer:
     """Exact full-batch training over full neighbourhoods: the reference's
     num_sample=None branch (models.py:280-289) put through loss.backward(),
@@ -1121,6 +1174,25 @@ class FullTrainer:
             dst.copy_(src)
         return self._embedder.embed(nodes)
 
+    def evaluate(self, nodes, field=None, want_logp=False):
+        """The model on `nodes` (unique ids, as forward_backward takes them)
+        under the current parameters, as an EvalResult: the forward stage
+        alone (embed(nodes, field=)'s call, with or without field(nodes)),
+        then the forward-only head hip_ops.cls_eval over H_L[nodes] and this
+        trainer's labels -- the NLL mean, the predictions (row i is nodes[i]),
+        the confusion matrix, and with want_logp the log-probabilities.  It
+        overwrites the step's activations in the workspace and nothing else:
+        parameters, gradients, optimiser state and the step counter stay as
+        they were, and nothing waits for the device until a metric is read.
+        The trainer does not range-check its labels; a row whose label lies
+        outside [0, n_classes) is left out and counted in n_bad."""
+        nodes = self._nodes(nodes)
+        self._forward_backward(nodes, _lib.GS_TF_FORWARD, field)
+        head = self.p.params[int(self.p.offsets[self.L]):]   # [Wc | bc], the tail of the flat buffer
+        loss, counts, pred, logp = ops.cls_eval(self.hidden(), self.labels, head, self.C, rows=nodes,
+                                                want_logp=want_logp)
+        return EvalResult(loss[0], counts[0], pred[0], None if logp is None else logp[0])
+
 
 class ClassifierProbe:
     """The linear probe of train_classification (utils.py:80-111) on frozen
@@ -1226,3 +1298,37 @@ class ClassifierProbe:
         S = snapshots.reshape(-1, C * D + C)
         W = S[:, :C * D].reshape(-1, C, D)
         return (torch.matmul(X, W.transpose(1, 2)) + S[:, None, C * D:]).argmax(2)
+
+    def evaluate(self, nodes, snapshots=None):
+        """hip_ops.cls_eval over the frozen rows `nodes` (ids in [0, N),
+        checked here) and their labels, as an EvalResult: under the current
+        parameters, or under every row of `snapshots` ([n_epochs, P], as run()
+        returns them) in one call -- every field then carries a leading epoch
+        dimension.  Where two logits tie, pred is the lower class.  Ids given
+        as a host array or list are checked on the host and nothing waits for
+        the device; a device tensor of ids is range-checked on the device,
+        which waits for it (as run() does for a device `order`)."""
+        if isinstance(nodes, torch.Tensor) and nodes.is_cuda:
+            ids = nodes.reshape(-1)
+            if ids.numel() < 1 or ids.dtype not in (torch.int32, torch.int64):
+                raise ValueError("ClassifierProbe.evaluate: nodes must hold at least one integer id")
+            if bool(((ids < 0) | (ids >= self.N)).any()):
+                raise IndexError("ClassifierProbe.evaluate: row id out of range")
+            ids = ids.to(device=self.device, dtype=torch.int32).contiguous()
+        else:
+            a = np.asarray(nodes.numpy() if isinstance(nodes, torch.Tensor) else nodes).reshape(-1)
+            if a.size < 1 or not np.issubdtype(a.dtype, np.integer):
+                raise ValueError("ClassifierProbe.evaluate: nodes must hold at least one integer id")
+            if a.min() < 0 or a.max() >= self.N:
+                raise IndexError("ClassifierProbe.evaluate: row id out of range")
+            ids = torch.from_numpy(a.astype(np.int32)).to(self.device)
+        P = self.p.params.numel()
+        if snapshots is None:
+            out = ops.cls_eval(self.E, self.labels, self.p.params, self.C, rows=ids)
+            return EvalResult(*(None if t is None else t[0] for t in out))
+        if not isinstance(snapshots, torch.Tensor) or snapshots.device != self.device or \
+                snapshots.dtype != torch.float32 or snapshots.numel() < P or snapshots.numel() % P:
+            raise ValueError("ClassifierProbe.evaluate: snapshots must be float32 [n_epochs, C*D + C] on the "
+                             "probe's device")
+        S = snapshots.reshape(-1, P).contiguous()
+        return EvalResult(*ops.cls_eval(self.E, self.labels, S.reshape(-1), self.C, rows=ids, n_sets=S.shape[0]))

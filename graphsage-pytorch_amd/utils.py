@@ -308,6 +308,33 @@ def evaluate(dataCenter, ds, graphSage, classification, device, max_vali_f1, nam
     return max_vali_f1
 
 
+def evaluate_full(dataCenter, ds, trainer, max_vali_f1, name, cur_epoch, use_field=True):
+    """evaluate's protocol (utils.py:13-57) on the exact path: validation
+    micro-F1 of `trainer` (a train.FullTrainer) over the validation ids, and,
+    when it improves on max_vali_f1, the test F1 and a checkpoint; the same
+    prints and the same return value.  F1 is EvalResult.micro_f1 of
+    FullTrainer.evaluate, over the receptive field of the ids (use_field) or
+    over all N rows.  What differs from evaluate: nothing is sampled, so no
+    `random` draw is made and no module is involved, and the checkpoint is
+    torch.save(trainer.state_dict()), not a pickled pair of modules."""
+    test_nodes = getattr(dataCenter, ds + "_test")
+    val_nodes = getattr(dataCenter, ds + "_val")
+
+    def f1_of(nodes):
+        ids = trainer._nodes(np.asarray(nodes))
+        return trainer.evaluate(ids, field=trainer.field(ids) if use_field else None).micro_f1
+
+    vali_f1 = f1_of(val_nodes)
+    print("Validation F1:", vali_f1)
+    if vali_f1 > max_vali_f1:
+        max_vali_f1 = vali_f1
+        test_f1 = f1_of(test_nodes)
+        print("Test F1:", test_f1)
+        os.makedirs("models", exist_ok=True)
+        torch.save(trainer.state_dict(), "models/model_best_{}_ep{}_{:.4f}.torch".format(name, cur_epoch, test_f1))
+    return max_vali_f1
+
+
 def micro_f1(labels, predicts):
     """Micro-averaged F1 of single-label multi-class predictions, which is the
     accuracy: every wrong prediction is one false positive (its class) and one

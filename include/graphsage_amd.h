@@ -580,6 +580,62 @@ int gs_cls_probe_run_ex(const float* E, int64_t lde, int64_t n_rows, int64_t D, 
                         float max_norm, float* snapshots, float* losses,
                         int64_t max_steps_per_launch, void* stream);
 
+/* The classifier head forward only, for evaluation: over B rows of H gathered
+ * by id, for each of n_sets parameter sets,
+ *   z = H[r]·Wcᵀ + bc,  logp = z - max - log Σ exp(z - max)  (max-shifted),
+ *   pred = the lowest class index among the maxima of z (np.argmax; a NaN logit
+ *          counts as maximal and the first NaN wins),
+ *   nll = -logp[y].
+ *   H        [*, D] fp32 rows with stride ldh >= D (device), never written
+ *   rows     NULL (row i of H) or [B] int32 row ids (device); not checked on
+ *            the device: the caller guarantees ids inside H
+ *   labels   int32 (device): row i's label is labels[rows[i]] when
+ *            labels_by_row != 0 and rows is given, else labels[i].  A label
+ *            outside [0, C) is never used as an index: its row is left out of
+ *            the loss and of the confusion matrix and counted in n_bad; its
+ *            pred and logp are still written
+ *   params   set s at params + s·set_stride (floats): Wc [C, D] row-major, then
+ *            bc [C] -- the tail of a trainer's flat parameter buffer, or the
+ *            probe's snapshots (set_stride = C·D + C)
+ *   pred     NULL or int32 [n_sets, B]
+ *   logp     NULL or fp32 [n_sets, B, C]
+ *   loss     fp32 [n_sets]: the mean of nll over the counted rows (NaN when
+ *            none is counted)
+ *   counts   int64 [n_sets, C·C + 2]: the confusion matrix counts[y·C + pred]
+ *            (row = true class), then n_counted and n_bad; zeroed by the call
+ *   ws       gs_cls_eval_ws_bytes(B, D, C, n_sets) bytes, 16-byte aligned: one
+ *            loss partial (a double) per set and chunk of 64 rows, and while
+ *            C·C <= 4096 one int32 [C·C + 2] histogram per set and workgroup
+ *            (at most 2048 workgroups per set, a function of B)
+ * Deterministic: the rows are cut into chunks of 64 by B alone, a chunk's terms
+ * are added in row order and a second launch adds the chunk partials in a fixed
+ * order; no floating-point atomics (the counts are integer sums of the
+ * workgroups' histograms, or integer atomics per row where C·C > 4096: neither
+ * has an order).  A set's outputs do not depend on n_sets or on the other
+ * sets.  Only pred, logp, loss, counts and ws are written.  Three launches
+ * (the rows, the counts, the loss; with C·C > 4096: zero the counts, the rows,
+ * the loss); nothing allocates or synchronises.
+ * Wc is staged in LDS while C·(D + 4) <= gs_cls_eval_wc_lds_floats() and the
+ * waves' row tiles fit beside it, and read through the cache otherwise; rows
+ * are read as float4 when D % 4 == 0, ldh % 4 == 0 and H is 16-byte aligned
+ * (and, where Wc is read through the cache, params is 16-byte aligned and
+ * set_stride % 4 == 0, for any n_sets), with scalar loads otherwise.  The load
+ * path is thus a property of (H, ldh, params, set_stride), never of n_sets;
+ * the two paths add a dot product in different orders.
+ * GS_EINVAL (before any launch): a NULL H / labels / params / loss / counts /
+ * ws, a size < 1, B >= 2^31, n_sets >= 2^16, C > 46340, ldh < D,
+ * set_stride < C·D + C, a workspace that is short or not 16-byte aligned, or
+ * D and C too large for the 64 KiB of LDS with Wc read through the cache:
+ * round4(C) + (C·C <= 4096 ? round4(C·C) : 0) + 4 + 4·(round4(D) + round4(C))
+ * floats must not exceed 16384 (D up to about 4,080 with few classes). */
+int64_t gs_cls_eval_wc_lds_floats(void);
+int64_t gs_cls_eval_ws_bytes(int64_t B, int64_t D, int64_t C, int64_t n_sets);
+int gs_cls_eval(int64_t B, int64_t D, int64_t C, const float* H, int64_t ldh,
+                const int32_t* rows, const int32_t* labels, int32_t labels_by_row,
+                const float* params, int64_t n_sets, int64_t set_stride, int32_t* pred,
+                float* logp, float* loss, int64_t* counts, void* ws, int64_t ws_bytes,
+                void* stream);
+
 /* f32 → bf16 (RNE) cast, n elements. */
 int gs_cast_f32_bf16(const float* in, void* out, int64_t n, void* stream);
 
