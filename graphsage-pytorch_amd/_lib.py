@@ -124,6 +124,13 @@ _SIGS = {
     "gs_cls_eval_ws_bytes": (_i64, [_i64, _i64, _i64, _i64]),
     "gs_cls_eval": (_i32, [_i64, _i64, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp,
                            _i64, _vp]),
+    "gs_cls_bce_supported": (_i32, [_i64, _i64]),
+    "gs_cls_bce_ws_bytes": (_i64, [_i64, _i64, _i64]),
+    "gs_cls_bce_fwd_bwd": (_i32, [_i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp,
+                                  _vp, _i64, _vp]),
+    "gs_cls_bce_eval_ws_bytes": (_i64, [_i64, _i64, _i64]),
+    "gs_cls_bce_eval": (_i32, [_i64, _i64, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                               _i64, _vp]),
     "gs_clip_sgd": (_i32, [_i32, _vp, _vp, _vp, _f32, _f32, _f32, _vp, _vp]),
     "gs_clip_adam": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i64, _vp,
                             _vp]),
@@ -256,8 +263,9 @@ class InferFullConfig(ctypes.Structure):
 class TrainFullConfig(ctypes.Structure):
     _fields_ = [
         ("n_layers", _i32), ("hidden", _i32), ("n_classes", _i32), ("agg", _i32), ("feat_dtype", _i32),
-        ("pad_", _i32), ("feat_dim", _i64), ("feat_ld", _i64), ("max_nodes", _i64), ("X", _vp), ("row_ptr", _vp),
+        ("head", _i32), ("feat_dim", _i64), ("feat_ld", _i64), ("max_nodes", _i64), ("X", _vp), ("row_ptr", _vp),
         ("col", _vp), ("t_row_ptr", _vp), ("t_col", _vp), ("labels", _vp), ("params", _vp), ("grads", _vp),
+        ("pos_weight", _vp),
     ]
 
 

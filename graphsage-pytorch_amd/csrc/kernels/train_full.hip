@@ -31,7 +31,7 @@ struct TrainLayout {
     int64_t w1lp = -1;
     int64_t a[GS_MAX_HOPS], h[GS_MAX_HOPS], am[GS_MAX_HOPS];  // A_l, H_l, argmax_l at index l - 1
     int64_t dh[2] = {0, 0}, dself = -1, da = 0, e = 0, de = 0, cls = 0, slab = 0, part = 0;
-    int64_t slab_bytes = 0, part_bytes = 0, total = 0;
+    int64_t slab_bytes = 0, part_bytes = 0, cls_bytes = 0, total = 0;
 };
 
 int64_t in_width(const gs_train_full_config& c, int l) {  // one concat half of layer l's input
@@ -46,6 +46,9 @@ void check_config(const FullPlan& p, const FullPlan& tp, const gs_train_full_con
     GS_REQUIRE(c.feat_dtype == GS_F32 || c.feat_dtype == GS_BF16, GS_EINVAL, "dtype must be f32 or bf16");
     GS_REQUIRE(c.feat_dim >= 1 && c.feat_dim < (1 << 28) && c.feat_ld >= c.feat_dim, GS_EINVAL, "bad feature shape");
     GS_REQUIRE(c.n_classes >= 1 && c.n_classes + c.hidden < 16384, GS_EINVAL, "bad class count");
+    GS_REQUIRE(c.head == 0 || c.head == 1, GS_EINVAL, "head: 0 = NLL, 1 = multi-label");
+    GS_REQUIRE(c.head == 0 || gs_cls_bce_supported(c.hidden, c.n_classes), GS_EINVAL,
+               "hidden and n_classes too large for the multi-label head (gs_cls_bce_supported)");
     GS_REQUIRE(p.n >= 1, GS_EINVAL, "empty graph");
     GS_REQUIRE(!p.transposed && tp.transposed && tp.n == p.n && tp.gcn == p.gcn, GS_EINVAL,
                "tplan must be the forward plan's transpose");
@@ -78,7 +81,9 @@ TrainLayout layout_of(const FullPlan& p, const FullPlan& tp, const gs_train_full
     }
     lo.e = take(c.max_nodes * H * 4);
     lo.de = take(c.max_nodes * H * 4);
-    lo.cls = take(gs_cls_nll_ws_floats(c.max_nodes, H, c.n_classes) * 4);
+    lo.cls_bytes = gs_cls_nll_ws_floats(c.max_nodes, H, c.n_classes) * 4;
+    if (c.head == 1) lo.cls_bytes = std::max(lo.cls_bytes, gs_cls_bce_ws_bytes(c.max_nodes, H, c.n_classes));
+    lo.cls = take(lo.cls_bytes);
     for (int l = 1; l <= L; ++l)
         lo.slab_bytes = std::max(lo.slab_bytes, gs_sage_linear_bwd_weight_ws(n, m * in_width(c, l), H));
     lo.slab = take(lo.slab_bytes);
@@ -144,6 +149,20 @@ __global__ __launch_bounds__(256) void head_combine_kernel(float* __restrict__ D
     }
     g = make_float4(e.x > 0.f ? g.x : 0.f, e.y > 0.f ? g.y : 0.f, e.z > 0.f ? g.z : 0.f, e.w > 0.f ? g.w : 0.f);
     reinterpret_cast<float4*>(D)[static_cast<int64_t>(r) * q + c] = g;
+}
+
+// The supervised head over the B gathered rows E (dense [B, H]): the NLL of one class per node, or under
+// c.head == 1 the multi-label BCE over the packed targets; dE comes back masked by relu'(E).
+void sup_head_launch(const gs_train_full_config& c, const TrainLayout& lo, int64_t B, const float* E,
+                     int64_t wc_off, int64_t bc_off, const int32_t* nodes, float* loss, float* dE, char* base,
+                     hipStream_t st) {
+    const int64_t H = c.hidden, C = c.n_classes;
+    if (c.head == 1)
+        ok(gs_cls_bce_fwd_bwd(B, H, C, E, H, c.params + wc_off, c.params + bc_off, c.labels, nodes, c.pos_weight, 1,
+                              loss, dE, c.grads + wc_off, c.grads + bc_off, base + lo.cls, lo.cls_bytes, st));
+    else
+        ok(gs_cls_nll_fwd_bwd(B, H, C, E, c.params + wc_off, c.params + bc_off, c.labels, nodes, 1, loss, dE,
+                              c.grads + wc_off, c.grads + bc_off, reinterpret_cast<float*>(base + lo.cls), st));
 }
 
 // The caller's buffer of the unsupervised head: the loss kernels' per-pair state, dE of the pair loss and the
@@ -275,8 +294,7 @@ void train_full_run(const FullPlan& p, const gs_full_plan_dev& d, const FullPlan
                              pairs, st));
         ok(gs_unsup_loss_bwd(u->M, u->P, u->N, B, H, fptr(lo.e), H, u->plan, pairs, one, de_net, H, st));
         if (u->with_sup)  // loss_sup over the whole extended batch, dE masked by relu'(H_L)
-            ok(gs_cls_nll_fwd_bwd(B, H, C, fptr(lo.e), c.params + wc_off, c.params + bc_off, c.labels, nodes, 1,
-                                  loss + 1, fptr(lo.de), c.grads + wc_off, c.grads + bc_off, fptr(lo.cls), st));
+            sup_head_launch(c, lo, B, fptr(lo.e), wc_off, bc_off, nodes, loss + 1, fptr(lo.de), base, st);
         else  // the classifier takes no part in this loss
             GS_REQUIRE(hipMemsetAsync(c.grads + wc_off, 0, (C * H + C) * 4, st) == hipSuccess, GS_EHIP,
                        "memset failed");
@@ -289,8 +307,7 @@ void train_full_run(const FullPlan& p, const gs_full_plan_dev& d, const FullPlan
         rows_by_id_kernel<false><<<dim3(grid), 256, 0, st>>>(fptr(lo.h[L - 1]), fptr(lo.e), nodes, B, q);
         check_launch(f ? "gs_train_full_field(gather)" : "gs_train_full(gather)");
         // dE masked by relu'(H_L): the rows of dZ_L, every other row of it zero
-        ok(gs_cls_nll_fwd_bwd(B, H, C, fptr(lo.e), c.params + wc_off, c.params + bc_off, c.labels, nodes, 1, loss,
-                              fptr(lo.de), c.grads + wc_off, c.grads + bc_off, fptr(lo.cls), st));
+        sup_head_launch(c, lo, B, fptr(lo.e), wc_off, bc_off, nodes, loss, fptr(lo.de), base, st);
         if (f) {  // dZ_L, compact: R_L is `nodes`, so every one of its n_L rows is written
             rows_by_map_kernel<<<dim3(grid), 256, 0, st>>>(dh_top, fptr(lo.de), nodes, fl[L].pos, B, q);
             check_launch("gs_train_full_field(scatter dE)");

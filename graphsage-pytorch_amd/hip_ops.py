@@ -837,6 +837,198 @@ def cls_eval_host(H, labels, params, C, rows=None, labels_by_row=True, n_sets=1,
     return loss, counts, pred, logp
 
 
+def multilabel_words(C):
+    """int32 words per node of packed multi-label targets: ceil(C / 32)."""
+    return (int(C) + 31) // 32
+
+
+def pack_multilabel(y):
+    """[N, C] hard multi-label targets (bool, uint8, or a 0/1 integer or float
+    tensor) as the packed int32 words [N, ceil(C / 32)] the multi-label head
+    reads: label c is bit c % 32 of word c // 32, the bits at or above C are
+    zero.  Torch ops on y's own device.  Anything other than 0 or 1 raises
+    ValueError (soft targets are out of scope)."""
+    if not isinstance(y, torch.Tensor) or y.dim() != 2 or y.shape[0] < 1 or y.shape[1] < 1:
+        raise ValueError("pack_multilabel: y must be a tensor [N, C] with N, C >= 1")
+    if y.dtype != torch.bool:
+        if y.dtype.is_complex or not bool(((y == 0) | (y == 1)).all()):
+            raise ValueError("pack_multilabel: targets must be 0 or 1 (soft targets are not supported)")
+        y = y != 0
+    N, C = y.shape
+    nW = multilabel_words(C)
+    bits = torch.zeros(N, nW * 32, dtype=torch.int64, device=y.device)
+    bits[:, :C] = y
+    shifts = torch.arange(32, dtype=torch.int64, device=y.device)
+    words = (bits.view(N, nW, 32) << shifts).sum(-1)           # in [0, 2^32)
+    words = torch.where(words >= 2 ** 31, words - 2 ** 32, words)  # the bit pattern as an int32
+    return words.to(torch.int32).contiguous()
+
+
+def unpack_multilabel(words, C):
+    """pack_multilabel's inverse: int32 [N, ceil(C / 32)] to bool [N, C] (bits at or above C are dropped)."""
+    C = int(C)
+    if not isinstance(words, torch.Tensor) or words.dtype != torch.int32 or words.dim() != 2 or C < 1 or \
+            words.shape[1] != multilabel_words(C):
+        raise ValueError("unpack_multilabel: words must be int32 [N, ceil(C / 32)]")
+    shifts = torch.arange(32, dtype=torch.int64, device=words.device)
+    bits = (words.to(torch.int64).unsqueeze(-1) >> shifts) & 1
+    return bits.reshape(words.shape[0], -1)[:, :C].bool()
+
+
+def cls_bce_supported(D, C):
+    """gs_cls_bce_supported: the multi-label head's LDS image and accumulators fit (no device work)."""
+    return bool(lib().gs_cls_bce_supported(int(D), int(C)))
+
+
+def _bce_params(name, Wc, bc, pos_weight, D):
+    if Wc.dtype != torch.float32 or Wc.dim() != 2 or not Wc.is_contiguous() or Wc.shape[1] != D or Wc.shape[0] < 1:
+        raise ValueError(f"{name}: Wc must be a contiguous float32 [C, D]")
+    C = int(Wc.shape[0])
+    if bc.dtype != torch.float32 or bc.dim() != 1 or not bc.is_contiguous() or bc.numel() != C:
+        raise ValueError(f"{name}: bc must be a contiguous float32 [C]")
+    if pos_weight is not None and (pos_weight.dtype != torch.float32 or pos_weight.dim() != 1 or
+                                   not pos_weight.is_contiguous() or pos_weight.numel() != C):
+        raise ValueError(f"{name}: pos_weight must be a contiguous float32 [C]")
+    if not cls_bce_supported(D, C):
+        raise ValueError(f"{name}: (D, C) = ({D}, {C}) does not fit the multi-label head (gs_cls_bce_supported)")
+    return C
+
+
+def _bce_targets(name, targets, C, n_min):
+    if _i32(targets).dim() != 2 or not targets.is_contiguous() or targets.shape[1] != multilabel_words(C) or \
+            targets.shape[0] < n_min:
+        raise ValueError(f"{name}: targets must be contiguous int32 [n, ceil(C / 32)] packed words "
+                         "(pack_multilabel), one row per node")
+
+
+def cls_bce(E, Wc, bc, targets, roots=None, pos_weight=None, mask_relu=False):
+    """The multi-label head, forward + backward (gs_cls_bce_fwd_bwd):
+    binary_cross_entropy_with_logits(E·Wcᵀ + bc, y, pos_weight=, reduction=
+    "mean") and its gradients.  E [B, D] fp32 with unit column stride (any row
+    stride); targets: packed int32 words (pack_multilabel), row i's are node
+    roots[i]'s (roots: [B] int32 ids, not checked here) or node i's;
+    mask_relu zeroes dE where E <= 0.  Returns (loss 0-d, dE [B, D], dWc
+    [C, D], dbc [C]) on the device; nothing waits for it."""
+    _dev(E, Wc, bc, targets, roots, pos_weight)
+    if E.dtype != torch.float32 or E.dim() != 2 or E.stride(1) != 1 or E.shape[0] < 1 or E.shape[1] < 1:
+        raise ValueError("cls_bce: E must be float32 [B, D] with unit column stride")
+    B, D = int(E.shape[0]), int(E.shape[1])
+    C = _bce_params("cls_bce", Wc, bc, pos_weight, D)
+    if roots is not None and (_i32(roots).dim() != 1 or not roots.is_contiguous() or roots.numel() != B):
+        raise ValueError("cls_bce: roots must be a contiguous int32 [B]")
+    _bce_targets("cls_bce", targets, C, 1 if roots is not None else B)
+    dev = E.device
+    need = int(lib().gs_cls_bce_ws_bytes(B, D, C))
+    if need < 0:
+        check(_lib.GS_EINVAL)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    dE = torch.empty(B, D, dtype=torch.float32, device=dev)
+    dWc = torch.empty(C, D, dtype=torch.float32, device=dev)
+    dbc = torch.empty(C, dtype=torch.float32, device=dev)
+    check(lib().gs_cls_bce_fwd_bwd(B, D, C, ptr(E), E.stride(0), ptr(Wc), ptr(bc), ptr(targets), ptr(roots),
+                                   ptr(pos_weight), int(bool(mask_relu)), ptr(loss), ptr(dE), ptr(dWc), ptr(dbc),
+                                   ptr(ws), need, _stream(E)))
+    return loss, dE, dWc, dbc
+
+
+def cls_bce_eval(H, targets, Wc, bc, rows=None, targets_by_row=True, pos_weight=None, want_pred=True,
+                 want_logits=False):
+    """The multi-label head forward only (gs_cls_bce_eval) over H[rows] (rows:
+    None, or [B] int32 ids into H, not checked here): the BCE mean, the
+    predictions z > 0 as packed words in the targets' layout, the per-label
+    counts and the number of rows with every label right.  Row i's targets are
+    node rows[i]'s (targets_by_row, with rows) or node i's.  Returns (loss
+    0-d, counts [C, 3] int64 -- true positives, false positives, false
+    negatives --, n_exact 0-d int64, pred [B, ceil(C / 32)] int32 or None,
+    logits [B, C] or None) on the device; counts and n_exact are views of one
+    buffer."""
+    _dev(H, targets, Wc, bc, rows, pos_weight)
+    if H.dtype != torch.float32 or H.dim() != 2 or H.stride(1) != 1 or H.shape[0] < 1 or H.shape[1] < 1:
+        raise ValueError("cls_bce_eval: H must be float32 [N, D] with unit column stride")
+    D = int(H.shape[1])
+    C = _bce_params("cls_bce_eval", Wc, bc, pos_weight, D)
+    if rows is not None and (_i32(rows).dim() != 1 or not rows.is_contiguous() or rows.numel() < 1):
+        raise ValueError("cls_bce_eval: rows must be a contiguous int32 vector of at least one id")
+    B = int(H.shape[0] if rows is None else rows.numel())
+    by_row = bool(targets_by_row) and rows is not None
+    _bce_targets("cls_bce_eval", targets, C, H.shape[0] if by_row else B)
+    dev = H.device
+    need = int(lib().gs_cls_bce_eval_ws_bytes(B, D, C))
+    if need < 0:
+        check(_lib.GS_EINVAL)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    counts = torch.empty(3 * C + 1, dtype=torch.int64, device=dev)
+    pred = torch.empty(B, multilabel_words(C), dtype=torch.int32, device=dev) if want_pred else None
+    logits = torch.empty(B, C, dtype=torch.float32, device=dev) if want_logits else None
+    check(lib().gs_cls_bce_eval(B, D, C, ptr(H), H.stride(0), ptr(rows), ptr(targets), int(by_row), ptr(Wc), ptr(bc),
+                                ptr(pos_weight), ptr(pred), ptr(logits), ptr(loss), ptr(counts), ptr(ws), need,
+                                _stream(H)))
+    return loss, counts[:3 * C].view(C, 3), counts[3 * C], pred, logits
+
+
+def _bce_host_args(name, X, Wc, bc, y, pos_weight, dt):
+    import numpy as np
+    X, Wc, bc = np.asarray(X, dt), np.asarray(Wc, dt), np.asarray(bc, dt).reshape(-1)
+    if X.ndim != 2 or Wc.ndim != 2 or Wc.shape[1] != X.shape[1] or bc.size != Wc.shape[0] or X.shape[0] < 1:
+        raise ValueError(f"{name}: E [B, D], Wc [C, D], bc [C]")
+    y = np.asarray(y)
+    if y.shape != (X.shape[0], Wc.shape[0]) or not np.isin(y, (0, 1)).all():
+        raise ValueError(f"{name}: y must be [B, C] of 0 / 1")
+    pw = np.ones(Wc.shape[0], dt) if pos_weight is None else np.asarray(pos_weight, dt).reshape(-1)
+    if pw.size != Wc.shape[0]:
+        raise ValueError(f"{name}: pos_weight [C]")
+    return X, Wc, bc, y.astype(dt), pw
+
+
+def _bce_host_terms(z, y, pw):
+    import numpy as np
+    w = 1.0 + (pw - 1.0) * y
+    e = np.exp(-np.abs(z))
+    l = (1.0 - y) * z + w * (np.log1p(e) + np.maximum(-z, 0.0))
+    sig = np.where(z >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+    return l, sig, w
+
+
+def cls_bce_host(E, Wc, bc, y, pos_weight=None, mask_relu=False, dtype=None):
+    """cls_bce in plain numpy, its CPU reference: the same function in `dtype`
+    (float64 by default) over unpacked targets y [B, C] of 0 / 1 (row i's own:
+    gather by roots before the call).  Returns (loss, dE, dWc, dbc, z)."""
+    import numpy as np
+    dt = np.dtype(np.float64 if dtype is None else dtype).type
+    X, Wc, bc, y, pw = _bce_host_args("cls_bce_host", E, Wc, bc, y, pos_weight, dt)
+    z = X @ Wc.T + bc
+    l, sig, w = _bce_host_terms(z, y, pw)
+    n = dt(z.size)
+    dz = (sig * w - pw * y) / n
+    dE = dz @ Wc
+    if mask_relu:
+        dE = np.where(X <= 0, dt(0), dE)
+    return l.sum(dtype=dt) / n, dE, dz.T @ X, dz.sum(0), z
+
+
+def cls_bce_eval_host(H, y, Wc, bc, rows=None, pos_weight=None, dtype=None):
+    """cls_bce_eval in plain numpy, its CPU reference: y [B, C] of 0 / 1 are the
+    evaluated rows' own targets.  Returns (loss, counts [C, 3] int64, n_exact,
+    pred bool [B, C], z [B, C])."""
+    import numpy as np
+    dt = np.dtype(np.float64 if dtype is None else dtype).type
+    H = np.asarray(H)
+    if rows is not None:
+        rows = np.asarray(rows, np.int64).reshape(-1)
+        if rows.size < 1 or rows.min() < 0 or rows.max() >= H.shape[0]:
+            raise IndexError("cls_bce_eval_host: row id out of range")
+        H = H[rows]
+    X, Wc, bc, y, pw = _bce_host_args("cls_bce_eval_host", H, Wc, bc, y, pos_weight, dt)
+    z = X @ Wc.T + bc
+    l, _sig, _w = _bce_host_terms(z, y, pw)
+    pred = z > 0
+    yb = y > 0
+    counts = np.stack([(pred & yb).sum(0), (pred & ~yb).sum(0), (~pred & yb).sum(0)], 1).astype(np.int64)
+    return l.sum(dtype=dt) / dt(z.size), counts, int((pred == yb).all(1).sum()), pred, z
+
+
 def unsup_loss_workspace(M, P, N, device):
     """The buffer unsup_loss_fwd leaves for unsup_loss_bwd: {coef, cos, n1, n2} per pair (the P positive
     pairs, then the N negative ones), then the M node scores at float offset 4 (P + N)."""

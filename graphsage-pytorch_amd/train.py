@@ -761,6 +761,62 @@ class EvalResult:
     per_class = property(lambda self: self._metrics()["per_class"])
 
 
+class MultiLabelEvalResult:
+    """What hip_ops.cls_bce_eval left on the device -- `loss` (the BCE mean
+    over rows x labels), `counts` ([C, 3] int64: true positives, false
+    positives, false negatives per label), `n_exact_dev` (the rows whose every
+    label is right), `pred_words` ([B, ceil(C / 32)] packed int32, z > 0) and
+    `logits` ([B, C], or None) -- and the metrics, computed on first use in
+    float64 from one download of the counts:
+
+        n_exact, subset_accuracy (n_exact / rows),
+        micro_f1 (2 TP / (2 TP + FP + FN) over all labels' sums),
+        macro_f1 (the plain mean of the per-label F1 over all C labels),
+        per_label: {"precision", "recall", "f1", "support"} arrays of C.
+
+    0 / 0 counts as 0 (sklearn's zero_division=0), as EvalResult does for an
+    absent class.  `pred` unpacks the predictions to bool [B, C] on request."""
+
+    def __init__(self, loss, counts, n_exact, pred_words, logits, n_rows, n_classes):
+        self.loss, self.counts, self.n_exact_dev = loss, counts, n_exact
+        self.pred_words, self.logits = pred_words, logits
+        self.n_rows, self.n_classes = int(n_rows), int(n_classes)
+        self._m = None
+
+    @staticmethod
+    def metrics_of(counts, n_exact, n_rows):
+        """The metrics from host counts [C, 3] (tp, fp, fn), n_exact and the row count."""
+        c = np.asarray(counts, np.int64)
+        tp, fp, fn = (c[:, k].astype(np.float64) for k in range(3))
+
+        def ratio(num, den):
+            den = np.asarray(den, np.float64)
+            return np.divide(num, den, out=np.zeros_like(den), where=den > 0)
+
+        f1 = ratio(2.0 * tp, 2.0 * tp + fp + fn)
+        micro = ratio(2.0 * tp.sum(), 2.0 * tp.sum() + fp.sum() + fn.sum())
+        return {"n_exact": int(n_exact), "subset_accuracy": float(n_exact) / float(n_rows),
+                "micro_f1": float(micro), "macro_f1": float(f1.mean()),
+                "per_label": {"precision": ratio(tp, tp + fp), "recall": ratio(tp, tp + fn), "f1": f1,
+                              "support": (c[:, 0] + c[:, 2])}}
+
+    def _metrics(self):
+        if self._m is None:
+            flat = torch.cat([self.counts.reshape(-1), self.n_exact_dev.reshape(1)]).cpu().numpy()  # the one download
+            self._m = self.metrics_of(flat[:-1].reshape(-1, 3), flat[-1], self.n_rows)
+        return self._m
+
+    @property
+    def pred(self):
+        return None if self.pred_words is None else ops.unpack_multilabel(self.pred_words, self.n_classes)
+
+    n_exact = property(lambda self: self._metrics()["n_exact"])
+    subset_accuracy = property(lambda self: self._metrics()["subset_accuracy"])
+    micro_f1 = property(lambda self: self._metrics()["micro_f1"])
+    macro_f1 = property(lambda self: self._metrics()["macro_f1"])
+    per_label = property(lambda self: self._metrics()["per_label"])
+
+
 class FullTrainer:
     """Exact full-batch training over full neighbourhoods: the reference's
     num_sample=None branch (models.py:280-289) put through loss.backward(),
@@ -827,11 +883,28 @@ class FullTrainer:
     ...) is one apply_model batch: extend, plan, field, step; nothing on this
     path draws from a `random` stream but extend_nodes itself.
 
+    head="multilabel": C independent sigmoid outputs per node under
+    binary_cross_entropy_with_logits (mean over nodes x labels, optional
+    `pos_weight` [C]) in place of log_softmax + NLL (gs_cls_bce_fwd_bwd).
+    `labels` is then a [N, C] multi-hot tensor of hard 0 / 1 targets (C ==
+    n_classes), packed at construction (hip_ops.pack_multilabel).  The
+    classifier keeps its shape, names and place in the flat buffer, so
+    state_dict, optimizer_state, apply_update, field, embed and cache_agg1
+    are untouched, step / forward_backward work full, with `field=` and with
+    `unsup=` ("plus_unsup" adds the BCE mean), and evaluate returns a
+    MultiLabelEvalResult.  head="nll" (the default) is the single-label head.
+    Out of scope for the multi-label head: the sampled path (NativeTrainer,
+    Runner, the GraphSage / Classification modules), ClassifierProbe, soft
+    targets.
+
     Single GPU.  Out of scope: data parallel."""
 
     def __init__(self, graph, features, labels, n_classes, num_layers=2, hidden=128, agg_func="MEAN", gcn=False,
                  lr=0.7, max_norm=5.0, seed=824, weights=None, optimizer="sgd", betas=(0.9, 0.999), eps=1e-8,
-                 weight_decay=0.0, seg_len=None, cache_agg1=True):
+                 weight_decay=0.0, seg_len=None, cache_agg1=True, head="nll", pos_weight=None):
+        if head not in ("nll", "multilabel"):
+            raise ValueError("FullTrainer: head must be 'nll' or 'multilabel'")
+        self.head = head
         self.optimizer = optimizer
         self._opt_kind = optimizer_kind(optimizer)
         self.betas, self.eps, self.weight_decay = (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
@@ -851,8 +924,21 @@ class FullTrainer:
             raise ValueError("features must be [n_nodes, F] fp32 or bf16 with unit column stride")
         self.graph, self.X, self.device = graph, features, features.device
         self.L, self.H, self.C, F = int(num_layers), int(hidden), int(n_classes), features.shape[1]
-        if labels.numel() != graph.n_nodes:
+        if head == "multilabel":
+            if not isinstance(labels, torch.Tensor) or labels.dim() != 2 or \
+                    tuple(labels.shape) != (graph.n_nodes, self.C):
+                raise ValueError("FullTrainer: with head='multilabel', labels must be a [n_nodes, n_classes] "
+                                 "multi-hot tensor")
+            if not ops.cls_bce_supported(self.H, self.C):
+                raise ValueError(f"FullTrainer: (hidden, n_classes) = ({self.H}, {self.C}) does not fit the "
+                                 "multi-label head (gs_cls_bce_supported)")
+        elif labels.dim() > 1 and labels.numel() != max(labels.shape):
+            raise ValueError("labels must hold one class per node (a [N, C] multi-hot tensor goes with "
+                             "head='multilabel')")
+        elif labels.numel() != graph.n_nodes:
             raise ValueError("labels must hold one class per node")
+        if pos_weight is not None and head != "multilabel":
+            raise ValueError("FullTrainer: pos_weight goes with head='multilabel'")
         if weights is None:
             weights = reference_init(self.L, F, self.H, self.C, gcn, seed)
         sage_w, cls_w, cls_b = weights
@@ -864,7 +950,16 @@ class FullTrainer:
         for i, (t, want) in enumerate(zip(tensors, shapes)):
             if tuple(t.shape) != want:
                 raise ValueError(f"weights[{i}] must be {list(want)}, got {list(t.shape)}")
-        self.labels = labels.reshape(-1).to(device=self.device, dtype=torch.int32)
+        self.pos_weight = None
+        if head == "multilabel":
+            self.labels = ops.pack_multilabel(labels.to(self.device))  # [N, ceil(C / 32)] packed words
+            if pos_weight is not None:
+                pw = torch.as_tensor(pos_weight, dtype=torch.float32).reshape(-1)
+                if pw.numel() != self.C:
+                    raise ValueError("FullTrainer: pos_weight must hold n_classes values")
+                self.pos_weight = pw.to(self.device).contiguous()
+        else:
+            self.labels = labels.reshape(-1).to(device=self.device, dtype=torch.int32)
         names = [f"sage_layer{i}.weight" for i in range(1, self.L + 1)] + ["layer.0.weight", "layer.0.bias"]
         self.p = FlatParams(tensors, names, [0, self.L], self.device)
         self.tplan = self.plan.transposed(ops.FULL_BWD_SEG_LEN if seg_len is None else seg_len)
@@ -882,7 +977,8 @@ class FullTrainer:
             feat_ld=features.stride(0), max_nodes=graph.n_nodes, X=features.data_ptr(),
             row_ptr=self.row_ptr.data_ptr(), col=self.col.data_ptr(), t_row_ptr=self.t_row_ptr.data_ptr(),
             t_col=self.t_col.data_ptr(), labels=self.labels.data_ptr(), params=self.p.params.data_ptr(),
-            grads=self.p.grads.data_ptr())
+            grads=self.p.grads.data_ptr(), head=1 if head == "multilabel" else 0,
+            pos_weight=None if self.pos_weight is None else self.pos_weight.data_ptr())
         need = int(lib().gs_train_full_ws_bytes(self.plan.handle, self.tplan.handle, ctypes.byref(self.cfg)))
         if need < 0:
             check(_lib.GS_EINVAL)
@@ -1188,6 +1284,13 @@ class FullTrainer:
         outside [0, n_classes) is left out and counted in n_bad."""
         nodes = self._nodes(nodes)
         self._forward_backward(nodes, _lib.GS_TF_FORWARD, field)
+        if self.head == "multilabel":
+            # the BCE mean, the packed predictions z > 0, the per-label counts: a MultiLabelEvalResult
+            # (want_logp: the logits)
+            loss, counts, n_exact, pred, logits = ops.cls_bce_eval(
+                self.hidden(), self.labels, self.p.view(self.L), self.p.view(self.L + 1), rows=nodes,
+                pos_weight=self.pos_weight, want_logits=want_logp)
+            return MultiLabelEvalResult(loss, counts, n_exact, pred, logits, nodes.numel(), self.C)
         head = self.p.params[int(self.p.offsets[self.L]):]   # [Wc | bc], the tail of the flat buffer
         loss, counts, pred, logp = ops.cls_eval(self.hidden(), self.labels, head, self.C, rows=nodes,
                                                 want_logp=want_logp)

@@ -636,6 +636,81 @@ int gs_cls_eval(int64_t B, int64_t D, int64_t C, const float* H, int64_t ldh,
                 float* logp, float* loss, int64_t* counts, void* ws, int64_t ws_bytes,
                 void* stream);
 
+/* The multi-label head: C independent sigmoid outputs per row under
+ * torch.nn.functional.binary_cross_entropy_with_logits(z, y, pos_weight=,
+ * reduction="mean") and its autograd, fused forward + backward.  The reference
+ * implementation has no multi-label head: this one has no counterpart there.
+ *   z = E·Wcᵀ + bc
+ *   l = (1 - y)·z + (1 + (pw - 1)·y)·(log1p(exp(-|z|)) + max(-z, 0))
+ *   loss = Σ l / (B·C)
+ *   dz = (σ(z)·(1 + (pw - 1)·y) - pw·y) / (B·C)
+ *   dE = dz·Wc (zeroed where E <= 0 when mask_relu != 0), dWc = dzᵀ·E, dbc = Σ_rows dz
+ *   E          [B, D] fp32 rows with stride lde >= D (device), never written
+ *   Wc, bc     [C, D] row-major and [C]
+ *   targets    hard 0/1 targets as packed bits: node v owns nW = ceil(C / 32)
+ *              int32 words at targets + v·nW, label c is bit c % 32 of word
+ *              c / 32; bits at or above C in the last word are ignored
+ *   roots      NULL (the targets of row i are node i's) or [B] int32 node ids
+ *              (node roots[i]'s); not checked on the device
+ *   pos_weight NULL (all ones) or [C]
+ *   loss[0], dE [B, D] (dense), dWc [C, D], dbc [C]: all overwritten
+ *   ws         gs_cls_bce_ws_bytes(B, D, C) bytes, 16-byte aligned: one double
+ *              and one [round16(C)][round16(D) + 16] fp32 slab per workgroup
+ *              (min(ceil(B / 16), 512) workgroups)
+ * No intermediate overflows for any finite z (exp is taken of -|z| only).
+ * Two launches: the row tiles (the three products on v_mfma_f32_16x16x4_f32,
+ * exact fp32 products, the loss and dz on the accumulator registers), then the
+ * sum of the workgroups' slabs in workgroup order.  No floating-point atomics:
+ * the result is bitwise repeatable and a function of (B, D, C) and the operands
+ * alone.  One code path for every shape: Wc and the rows are zero-padded in
+ * LDS, and every staging load is a scalar one, so no alignment is asked of E,
+ * lde, Wc or D.
+ * gs_cls_bce_supported(D, C): 1 / 0, no device work.  With CP = round16(C),
+ * D16 = round16(D), nW = ceil(C / 32), in floats of the workgroup's 160 KiB of
+ * LDS:
+ *   CP·(D16 + 4) + 2·CP + 16·(D16 + 4) + 16·(CP + 4) + 32·nW + 3·CP + 16 <= 40960
+ * (the last sum rounded up to a multiple of 4 before the 16), and the
+ * accumulator tiles of dWc and dbc must fit the registers:
+ *   CP/16 · (D16/16 + 1) <= 144.
+ * D = 128 with C = 128 and D = 256 with C = 128 fit; at D = 64 the largest C is
+ * 432.
+ * GS_EINVAL (before any launch): a NULL E / Wc / bc / targets / loss / dE / dWc
+ * / dbc / ws, a size < 1, B >= 2^31, lde < D, an unsupported (D, C), a
+ * workspace that is short or not 16-byte aligned. */
+int gs_cls_bce_supported(int64_t D, int64_t C);
+int64_t gs_cls_bce_ws_bytes(int64_t B, int64_t D, int64_t C);
+int gs_cls_bce_fwd_bwd(int64_t B, int64_t D, int64_t C, const float* E, int64_t lde,
+                       const float* Wc, const float* bc, const int32_t* targets,
+                       const int32_t* roots, const float* pos_weight, int32_t mask_relu,
+                       float* loss, float* dE, float* dWc, float* dbc, void* ws,
+                       int64_t ws_bytes, void* stream);
+
+/* The multi-label head forward only, for evaluation (one parameter set): over B
+ * rows of H gathered by id as in gs_cls_eval,
+ *   z = H[r]·Wcᵀ + bc, the BCE mean of gs_cls_bce_fwd_bwd, pred = z > 0
+ *   (σ(z) > 0.5; z == 0 and a NaN predict 0).
+ *   rows     NULL (row i of H) or [B] int32 row ids; not checked on the device
+ *   targets  packed as above; row i's are node rows[i]'s when targets_by_row != 0
+ *            and rows is given, else node i's
+ *   pred     NULL or int32 [B, nW]: the predictions in the targets' layout, the
+ *            bits at or above C zero
+ *   logits   NULL or fp32 [B, C]
+ *   loss     fp32 [1]
+ *   counts   int64 [3·C + 1]: per label the true positives, false positives and
+ *            false negatives (counts[3 c + k]), then n_exact, the number of rows
+ *            whose every label is right
+ *   ws       gs_cls_bce_eval_ws_bytes(B, D, C) bytes, 16-byte aligned
+ * The counts are integer sums and exact; the loss is a fixed-order sum (double
+ * over the tiles and workgroups, rounded once).  Two launches.  The limits and
+ * refusals of gs_cls_bce_fwd_bwd (NULL H / Wc / bc / targets / loss / counts /
+ * ws, ldh < D). */
+int64_t gs_cls_bce_eval_ws_bytes(int64_t B, int64_t D, int64_t C);
+int gs_cls_bce_eval(int64_t B, int64_t D, int64_t C, const float* H, int64_t ldh,
+                    const int32_t* rows, const int32_t* targets, int32_t targets_by_row,
+                    const float* Wc, const float* bc, const float* pos_weight, int32_t* pred,
+                    float* logits, float* loss, int64_t* counts, void* ws, int64_t ws_bytes,
+                    void* stream);
+
 /* f32 → bf16 (RNE) cast, n elements. */
 int gs_cast_f32_bf16(const float* in, void* out, int64_t n, void* stream);
 
@@ -1073,6 +1148,9 @@ int gs_agg_full_bwd(const gs_full_plan* tplan, const gs_full_plan_dev* tdev, gs_
  *            aggregate and W_1 rounded to bf16, the layers above in fp32.
  *   head     E = H_L[nodes] (n_nodes unique device ids), gs_cls_nll_fwd_bwd with
  *            roots = nodes (loss = NLL mean over nodes), dE scattered into a zeroed dH_L.
+ *            cfg->head == 1: gs_cls_bce_fwd_bwd in its place (the BCE mean over nodes x
+ *            n_classes, labels = the packed targets, cfg->pos_weight); the shape must
+ *            pass gs_cls_bce_supported(hidden, n_classes).
  *   backward l = L..1: dW_l, then for l >= 2 [dSelf | dA] = dH_l W_l and
  *            dH_{l-1} = gs_agg_full_bwd(dA, dSelf, relu mask of H_{l-1}).
  * params / grads: the flat fp32 layout [W_1 | .. | W_L | Wc | bc] (W_l
@@ -1085,7 +1163,7 @@ typedef struct {
     int32_t n_layers, hidden, n_classes;
     int32_t agg;             /* gs_agg */
     int32_t feat_dtype;      /* gs_dtype */
-    int32_t pad_;
+    int32_t head;            /* 0: NLL over one class per node; 1: multi-label (gs_cls_bce_fwd_bwd) */
     int64_t feat_dim, feat_ld;
     int64_t max_nodes;       /* capacity of the loss head (rows of `nodes`) */
     const void* X;
@@ -1093,9 +1171,10 @@ typedef struct {
     const int32_t* col;
     const int64_t* t_row_ptr;/* device CSR of the transposed plan */
     const int32_t* t_col;
-    const int32_t* labels;   /* [n] device */
+    const int32_t* labels;   /* [n] device; head 1: the packed targets [n, ceil(n_classes / 32)] */
     const float* params;
     float* grads;
+    const float* pos_weight; /* head 1: NULL (ones) or [n_classes] device; head 0: ignored */
 } gs_train_full_config;
 enum { GS_TF_FORWARD = 1, GS_TF_HEAD = 2, GS_TF_BACKWARD = 4, GS_TF_ALL = 7 };
 /* Byte offsets into ws of the kept activations (which: 0 = H_l, 1 = A_l, 2 = dH_l, the ping-pong buffer
@@ -1202,7 +1281,7 @@ int gs_train_full_field_forward_backward(const gs_full_plan* plan, const gs_full
  * for all N rows, or the field of `nodes`.  Head:
  *   E = H_L[nodes]; loss_net = gs_unsup_loss_fwd(E), dE_net = gs_unsup_loss_bwd
  *   (lde = hidden, dloss = 1); with_sup: loss_sup and the classifier's gradients
- *   from gs_cls_nll_fwd_bwd over the same U rows, otherwise the classifier's
+ *   from gs_cls_nll_fwd_bwd (cfg->head == 1: gs_cls_bce_fwd_bwd) over the same U rows, otherwise the classifier's
  *   range of grads is set to zero; then one launch writes
  *   dZ_L[target(i)] = E[i] > 0 ? dE_sup[i] + dE_net[i] : 0
  *   (target(i) = nodes[i] in a zeroed dH_L, or POS_L[nodes[i]] in the compact one)
