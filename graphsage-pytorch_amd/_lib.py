@@ -203,6 +203,7 @@ _SIGS = {
     "gs_full_plan_destroy": (None, [_vp]),
     "gs_full_plan_dims": (_i32, [_vp, _vp]),
     "gs_full_plan_array": (_vp, [_vp, _i32]),
+    "gs_full_plan_edge_denom": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "gs_agg_full_ws_bytes": (_i64, [_vp, _i64, _i64, _i64]),
     "gs_agg_full": (_i32, [_vp, _vp, _i32, _i32, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64,
                            _vp]),
@@ -238,6 +239,7 @@ _SIGS = {
 (GS_FP_ITEMS, GS_FP_ITEM_PTR, GS_FP_SLOT_PTR, GS_FP_SPLIT_PTR, GS_FP_SPLIT_ROWS, GS_FP_COUNT, GS_FP_SELF_LOOP,
  GS_FP_EMPTY_ROWS) = range(8)
 GS_FP_T_ROW_PTR, GS_FP_T_COL = 8, 9  # a transposed plan's own CSR (gs_full_plan_transpose)
+GS_FP_T_SRC = 10  # int64: the forward entry behind each transposed entry, -1 for the self entry gcn added
 GS_TF_FORWARD, GS_TF_HEAD, GS_TF_BACKWARD, GS_TF_ALL = 1, 2, 4, 7
 # a receptive field (gs_full_field_*): counts[l] = n_l, counts[GS_FF_LAYER0 + 4 (l - 1) + k] per layer
 GS_FF_LAYER0, GS_FF_NCOUNTS = GS_MAX_HOPS + 1, GS_MAX_HOPS + 1 + 4 * GS_MAX_HOPS
@@ -245,7 +247,9 @@ GS_FF_ROWS, GS_FF_POS, GS_FF_ITEMS, GS_FF_SPLIT, GS_FF_T_ITEMS, GS_FF_T_SPLIT = 
 
 
 class FullPlanDev(ctypes.Structure):
-    _fields_ = [("items", _vp), ("slot_ptr", _vp), ("split_rows", _vp), ("count", _vp), ("self_loop", _vp)]
+    # weight / denom / self_weight: per-edge weights (hip_ops.EdgeWeights); all NULL is the unweighted aggregate
+    _fields_ = [("items", _vp), ("slot_ptr", _vp), ("split_rows", _vp), ("count", _vp), ("self_loop", _vp),
+                ("weight", _vp), ("denom", _vp), ("self_weight", _vp)]
 
 
 class FullField(ctypes.Structure):

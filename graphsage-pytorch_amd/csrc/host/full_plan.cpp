@@ -22,7 +22,10 @@
 // forward row repeats repeated here), under the forward's rules -- a row's own
 // id is dropped, and under gcn v is a destination of itself exactly once --
 // and plans it like a forward CSR, at a seg_len of its own.  Symmetry of the
-// input is never assumed.
+// input is never assumed.  The same pass records t_src: the forward entry
+// each transposed entry came from (-1 for the self entry gcn adds to a row
+// without a self loop), so per-edge weights in forward order can be permuted
+// into transposed order, and replaced, without another plan.
 #include "full_plan.hpp"
 
 #include <algorithm>
@@ -92,14 +95,24 @@ FullPlan* full_plan_transpose(const FullPlan& fwd, const int64_t* row_ptr, const
     }
     for (int64_t u = 0; u < n; ++u) trp[u + 1] += trp[u];
     std::vector<int32_t> tcol(static_cast<size_t>(n ? trp[n] : 0));
+    std::vector<int64_t> tsrc(tcol.size());
     std::vector<int64_t> fill(trp.begin(), trp.end() - 1);
     for (int64_t v = 0; v < n; ++v) {  // ascending v: every transposed row ends up ascending
+        int64_t self_t = -1;  // the row's (first) self entry
         for (int64_t t = row_ptr[v]; t < row_ptr[v + 1]; ++t) {
             const int32_t u = col[t];
-            if (u != v) tcol[fill[u]++] = static_cast<int32_t>(v);
+            if (u != v) {
+                tsrc[fill[u]] = t;
+                tcol[fill[u]++] = static_cast<int32_t>(v);
+            } else if (self_t < 0) {
+                self_t = t;
+            }
         }
         // v's own entry: every smaller destination of v is already in place and every larger one comes later
-        if (fwd.gcn) tcol[fill[v]++] = static_cast<int32_t>(v);
+        if (fwd.gcn) {
+            tsrc[fill[v]] = self_t;
+            tcol[fill[v]++] = static_cast<int32_t>(v);
+        }
     }
     std::unique_ptr<FullPlan> p(full_plan_build(trp.data(), tcol.data(), n, 0, seg_len));
     p->gcn = fwd.gcn;
@@ -109,6 +122,7 @@ FullPlan* full_plan_transpose(const FullPlan& fwd, const int64_t* row_ptr, const
     p->empty_rows.clear();
     p->t_row_ptr = std::move(trp);
     p->t_col = std::move(tcol);
+    p->t_src = std::move(tsrc);
     return p.release();
 }
 
@@ -170,8 +184,27 @@ const void* gs_full_plan_array(const gs_full_plan* plan, int32_t which) {
         case GS_FP_EMPTY_ROWS: return p.empty_rows.data();
         case GS_FP_T_ROW_PTR: return p.transposed ? p.t_row_ptr.data() : nullptr;
         case GS_FP_T_COL: return p.transposed ? p.t_col.data() : nullptr;
+        case GS_FP_T_SRC: return p.transposed ? p.t_src.data() : nullptr;
         default: return nullptr;
     }
+}
+
+int gs_full_plan_edge_denom(const gs_full_plan* plan, const int64_t* row_ptr, const int32_t* col, const float* w,
+                            const float* self_weight, float* den) {
+    GS_API_BEGIN
+    GS_REQUIRE(plan && row_ptr && den, GS_EINVAL, "NULL argument");
+    const gs::FullPlan& p = *reinterpret_cast<const gs::FullPlan*>(plan);
+    GS_REQUIRE(!p.transposed, GS_EINVAL, "a forward plan expected");
+    GS_REQUIRE((p.n ? row_ptr[p.n] : 0) == p.n_entries && (p.n_entries == 0 || (col && w)), GS_EINVAL,
+               "the CSR is not the plan's");
+    for (int64_t v = 0; v < p.n; ++v) {
+        double s = 0.0;  // entry order, one rounding at the end: float(COUNT) for unit weights
+        for (int64_t t = row_ptr[v]; t < row_ptr[v + 1]; ++t)
+            if (p.gcn || col[t] != v) s += static_cast<double>(w[t]);
+        if (p.gcn && !p.self_loop[v]) s += self_weight ? static_cast<double>(self_weight[v]) : 1.0;
+        den[v] = static_cast<float>(s);
+    }
+    GS_API_END
 }
 
 }  // extern "C"

@@ -25,6 +25,7 @@ struct FullPlan {
     bool transposed = false;
     std::vector<int64_t> t_row_ptr;   // [n + 1]
     std::vector<int32_t> t_col;       // [t_row_ptr[n]]
+    std::vector<int64_t> t_src;       // [t_row_ptr[n]]: the forward entry behind each one, -1: the self entry gcn added
 };
 
 // Throws gs::Error; seg_len <= 0: no row is split.

@@ -18,6 +18,16 @@
 // (full_field.hip).  The items and split rows are the field's, and a row is
 // written to row pos[v] of a compact output; the walk, the partial slots and
 // the combine order are the same, so a row is bitwise the unmapped one.
+//
+// WT (a template parameter of both kernels, MEAN only): per-edge weights.  The
+// lane that loads col[e] loads w[e] beside it (the same index: coalesced), the
+// weight is shuffled to the group like the row id -- when its row is
+// accumulated, after the loads, so that it holds no register across them --
+// and the accumulate is acc = fmaf(w, x, acc) in the same visiting order; gcn's appended self row
+// takes sw[v], and the row is divided by den[v] (the weights' sum, from the
+// caller) or, with den NULL, left as the weighted sum.  fmaf(1, x, acc) is
+// acc + x, so unit weights with den = float(cnt) give the WT = false bits.
+// The WT = false instantiations hold none of this.
 #include "agg_dev.hpp"
 #include "agg_full.hpp"
 
@@ -25,7 +35,7 @@
 
 namespace gs {
 
-template <int OP, typename T, int VEC, int G, bool MAP>
+template <int OP, typename T, int VEC, int G, bool MAP, bool WT>
 __global__ __launch_bounds__(kBlock) void agg_full_kernel(const T* __restrict__ X, T* __restrict__ out, FullArgs a) {
     const int gl = threadIdx.x % G;
     const int li = blockIdx.x * (kBlock / G) + threadIdx.x / G;
@@ -50,6 +60,8 @@ __global__ __launch_bounds__(kBlock) void agg_full_kernel(const T* __restrict__ 
             const bool mine = gl < m;
             const int nb = a.col[mine ? base + gl : base];
             const int my = (mine && (gcn || nb != node)) ? nb : -1;  // self is skipped unless gcn
+            float wf = 0.f;
+            if constexpr (WT) wf = a.w[mine ? base + gl : base];
             for (int j = 0; j < m; j += kRows) {
                 int rows[kRows];
                 bool ok[kRows];
@@ -65,9 +77,12 @@ __global__ __launch_bounds__(kBlock) void agg_full_kernel(const T* __restrict__ 
                     RowIO<T, VEC>::load(X + static_cast<int64_t>(ok[u] ? rows[u] : fallback) * a.ldx + f0c, x[u]);
 #pragma unroll
                 for (int u = 0; u < kRows; ++u) {
+                    float wu = 0.f;  // the weight joins its row here, after the loads: it holds no register across them
+                    if constexpr (WT) wu = __shfl(wf, j + u < m ? j + u : j, G);
 #pragma unroll
                     for (int v = 0; v < VEC; ++v) {
-                        if (OP == GS_AGG_MEAN) acc[v] += ok[u] ? x[u][v] : 0.f;
+                        if constexpr (WT) acc[v] = fmaf(wu, ok[u] ? x[u][v] : 0.f, acc[v]);
+                        else if (OP == GS_AGG_MEAN) acc[v] += ok[u] ? x[u][v] : 0.f;
                         else acc[v] = (ok[u] && x[u][v] > acc[v]) ? x[u][v] : acc[v];
                     }
                 }
@@ -80,14 +95,23 @@ __global__ __launch_bounds__(kBlock) void agg_full_kernel(const T* __restrict__ 
         if (gcn && !a.self_loop[node]) {  // gcn keeps self exactly once (set semantics)
             float x[VEC];
             RowIO<T, VEC>::load(X + static_cast<int64_t>(node) * a.ldx + f0c, x);
+            float sw = 1.f;
+            if constexpr (WT) sw = a.sw ? a.sw[node] : 1.f;
 #pragma unroll
             for (int v = 0; v < VEC; ++v) {
-                if (OP == GS_AGG_MEAN) acc[v] += x[v];
+                if constexpr (WT) acc[v] = fmaf(sw, x[v], acc[v]);
+                else if (OP == GS_AGG_MEAN) acc[v] += x[v];
                 else acc[v] = x[v] > acc[v] ? x[v] : acc[v];
             }
         }
         if (!act) continue;
-        if (OP == GS_AGG_MEAN) {
+        if constexpr (WT) {
+            if (a.den) {  // the weighted mean: the same true division, by the weights' sum
+                const float c = a.den[node];
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) acc[v] /= c;
+            }
+        } else if (OP == GS_AGG_MEAN) {
             // a true division (one rounding, as the reference's sum / count), not a product with a rounded
             // reciprocal: a bf16 output flips to the neighbouring value less often; count 0 -> NaN row (0/0, :313)
             const float c = static_cast<float>(a.cnt[node]);
@@ -99,8 +123,9 @@ __global__ __launch_bounds__(kBlock) void agg_full_kernel(const T* __restrict__ 
 }
 
 // One lane group per split row: its partials in segment order, four loads in
-// flight, then gcn's self row, the mean's division and the output row.
-template <int OP, typename T, int VEC, int G, bool MAP>
+// flight, then gcn's self row (WT: times its weight), the mean's division (WT:
+// by den, if any) and the output row.
+template <int OP, typename T, int VEC, int G, bool MAP, bool WT>
 __global__ __launch_bounds__(kBlock) void agg_full_combine_kernel(const T* __restrict__ X, T* __restrict__ out,
                                                                   FullArgs a) {
     constexpr int NP = 4;
@@ -137,13 +162,22 @@ __global__ __launch_bounds__(kBlock) void agg_full_combine_kernel(const T* __res
         if (a.gcn && !a.self_loop[node]) {
             float x[VEC];
             RowIO<T, VEC>::load(X + static_cast<int64_t>(node) * a.ldx + f0, x);
+            float sw = 1.f;
+            if constexpr (WT) sw = a.sw ? a.sw[node] : 1.f;
 #pragma unroll
             for (int v = 0; v < VEC; ++v) {
-                if (OP == GS_AGG_MEAN) acc[v] += x[v];
+                if constexpr (WT) acc[v] = fmaf(sw, x[v], acc[v]);
+                else if (OP == GS_AGG_MEAN) acc[v] += x[v];
                 else acc[v] = x[v] > acc[v] ? x[v] : acc[v];
             }
         }
-        if (OP == GS_AGG_MEAN) {
+        if constexpr (WT) {
+            if (a.den) {
+                const float c = a.den[node];
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) acc[v] /= c;
+            }
+        } else if (OP == GS_AGG_MEAN) {
             const float c = static_cast<float>(a.cnt[node]);
 #pragma unroll
             for (int v = 0; v < VEC; ++v) acc[v] /= c;
@@ -156,9 +190,21 @@ template <int OP, typename T>
 static void launch_full_t(bool vec, const T* X, T* out, const FullArgs& a, hipStream_t st) {
     with_group<sizeof(T) == 4 ? 4 : 8>(vec, a.F, [&](auto vc, auto gc) {
         constexpr int VEC = decltype(vc)::value, G = decltype(gc)::value;
-        launch_walk_combine<G>(a.pos != nullptr, a.n_items, a.n_split, st, agg_full_kernel<OP, T, VEC, G, true>,
-                               agg_full_combine_kernel<OP, T, VEC, G, true>, agg_full_kernel<OP, T, VEC, G, false>,
-                               agg_full_combine_kernel<OP, T, VEC, G, false>, X, out, a);
+        if constexpr (OP == GS_AGG_MEAN) {
+            if (a.w) {
+                launch_walk_combine<G>(a.pos != nullptr, a.n_items, a.n_split, st,
+                                       agg_full_kernel<OP, T, VEC, G, true, true>,
+                                       agg_full_combine_kernel<OP, T, VEC, G, true, true>,
+                                       agg_full_kernel<OP, T, VEC, G, false, true>,
+                                       agg_full_combine_kernel<OP, T, VEC, G, false, true>, X, out, a);
+                return;
+            }
+        }
+        launch_walk_combine<G>(a.pos != nullptr, a.n_items, a.n_split, st,
+                               agg_full_kernel<OP, T, VEC, G, true, false>,
+                               agg_full_combine_kernel<OP, T, VEC, G, true, false>,
+                               agg_full_kernel<OP, T, VEC, G, false, false>,
+                               agg_full_combine_kernel<OP, T, VEC, G, false, false>, X, out, a);
     });
 }
 
@@ -191,6 +237,10 @@ FullArgs full_args(const FullPlan& p, const gs_full_plan_dev& d, const int64_t* 
     a.cnt = d.count;
     a.self_loop = d.self_loop;
     a.pos = fl ? fl->pos : nullptr;
+    GS_REQUIRE(d.weight || (!d.denom && !d.self_weight), GS_EINVAL, "denom / self_weight without weight");
+    a.w = d.weight;
+    a.den = d.denom;
+    a.sw = d.self_weight;
     a.part = static_cast<float*>(ws);
     a.slot0 = p.slot_ptr[row0];
     a.seg_len = std::min<int64_t>(p.seg_len, (int64_t(1) << 31) - 1);
@@ -206,6 +256,8 @@ void agg_full_launch(const FullPlan& p, const gs_full_plan_dev& d, gs_agg op, gs
                      int64_t ldo, void* ws, int64_t ws_bytes, hipStream_t st, const FieldLayer* fl) {
     GS_REQUIRE(op == GS_AGG_MEAN || op == GS_AGG_MAX, GS_EINVAL, "agg_func must be MEAN or MAX");
     GS_REQUIRE(dt == GS_F32 || dt == GS_BF16, GS_EINVAL, "dtype must be f32 or bf16");
+    GS_REQUIRE(op != GS_AGG_MAX || !d.weight, GS_EINVAL, "edge weights go with MEAN, not MAX");
+    GS_REQUIRE(!d.weight || !p.transposed, GS_EINVAL, "a forward plan expected");
     const int64_t need = agg_full_ws_need(p, F, row0, n_rows);
     GS_REQUIRE(ldx >= F && ldo >= F, GS_EINVAL, "leading dimension smaller than F");
     if (n_rows == 0) return;

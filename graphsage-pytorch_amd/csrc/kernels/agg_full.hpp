@@ -49,6 +49,9 @@ struct FullArgs {
     const int* cnt;
     const uint8_t* self_loop;
     const int* pos;         // MAP kernels: the output row of a node (a field's pos_l); NULL otherwise
+    const float* w;         // WT kernels: a weight per CSR entry (NULL: the unweighted kernels run)
+    const float* den;       // WT kernels: the weighted mean's divisor per row; NULL: the weighted sum
+    const float* sw;        // WT kernels: the weight of gcn's appended self row; NULL: 1
     float* part;
     int64_t slot0;          // slot_ptr[row0]: the window's partials start at part[0]
     int64_t seg_len;        // clamped to 2^31 - 1

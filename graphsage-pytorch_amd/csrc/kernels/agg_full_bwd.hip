@@ -25,6 +25,15 @@
 // R_l like a slot past the segment, reads dA and argmax at row pos_l[v] (the
 // divisor cnt[v] and the compared ids stay global), adds dSelf[pos_l[u]]
 // only where u is in R_l, and writes row pos_{l-1}[u] of a compact dH.
+//
+// WM (a template parameter of the MEAN backward walk): per-edge weights in the
+// transposed plan's entry order.  The lane that loads t_col[e] loads w_t[e]
+// and, for the weighted mean (WM == 1), den[v] in place of cnt[v]; den is
+// shuffled with the row id as cnt is, the weight when its row is accumulated
+// (it then holds no register across the loads: the weighted walk keeps the
+// unweighted one's occupancy), and acc = fmaf(w, dA[v] / den[v], acc).  WM == 2
+// is the weighted sum: no divisor and no division.  WM == 0 is the unweighted
+// kernel, unchanged; unit weights with den = float(cnt) give its bits.
 #include "agg_dev.hpp"
 #include "agg_full.hpp"
 
@@ -221,6 +230,8 @@ struct BwdArgs {
     const int64_t* slot_ptr;
     const int* split_rows;
     const int* cnt;          // the forward's effective neighbour counts
+    const float* w;          // WM != 0: a weight per transposed entry
+    const float* den;        // WM == 1: the weighted mean's divisor per destination
     const float* dA;
     const float* dSelf;      // may be NULL
     int64_t ldd;
@@ -257,7 +268,7 @@ __device__ __forceinline__ void bwd_finish(const BwdArgs& a, int node, int f0, f
     else RowIO<float, VEC>::store(a.dH + static_cast<int64_t>(node) * a.ldh + f0, acc);
 }
 
-template <int OP, int VEC, int G, bool MAP>
+template <int OP, int VEC, int G, bool MAP, int WM>
 __global__ __launch_bounds__(kBlock) void agg_full_bwd_kernel(BwdArgs a) {
     constexpr int NR = OP == GS_AGG_MAX ? kRows / 2 : kRows;  // MAX loads an id row beside every gradient row
     const int gl = threadIdx.x % G;
@@ -284,8 +295,11 @@ __global__ __launch_bounds__(kBlock) void agg_full_bwd_kernel(BwdArgs a) {
             const int64_t e = mine ? base + gl : base;
             const int nb = a.col[e];
             int my = mine ? nb : -1;
-            float cf = 1.f;
-            if (OP == GS_AGG_MEAN) cf = static_cast<float>(a.cnt[nb]);
+            float cf = 1.f, wf = 0.f;
+            if constexpr (WM != 0) wf = a.w[e];
+            if constexpr (WM == 1) cf = a.den[nb];
+            else if constexpr (WM == 2) cf = 1.f;
+            else if (OP == GS_AGG_MEAN) cf = static_cast<float>(a.cnt[nb]);
             // MAX routes a destination's gradient once, however often its row names this source (the
             // transposed row is ascending: repeats are neighbours, across a segment boundary too)
             else if (e > rb && a.col[e - 1] == nb) my = -1;
@@ -298,7 +312,7 @@ __global__ __launch_bounds__(kBlock) void agg_full_bwd_kernel(BwdArgs a) {
                 for (int u = 0; u < NR; ++u) {
                     const int src = j + u < m ? j + u : j;
                     rows[u] = __shfl(my, src, G);
-                    if constexpr (OP == GS_AGG_MEAN) c[u] = __shfl(cf, src, G);
+                    if constexpr (OP == GS_AGG_MEAN && WM == 0) c[u] = __shfl(cf, src, G);
                     ok[u] = (j + u < m) && rows[u] >= 0;
                 }
                 const int fallback = rows[0] >= 0 ? rows[0] : (MAP ? 0 : node);  // R_l is never empty
@@ -312,10 +326,16 @@ __global__ __launch_bounds__(kBlock) void agg_full_bwd_kernel(BwdArgs a) {
                 }
 #pragma unroll
                 for (int u = 0; u < NR; ++u) {
-                    const float r = (OP == GS_AGG_MEAN && GS_FULL_BWD_QUOT_MODE != 0) ? 1.0f / c[u] : 0.f;
+                    float wu = 0.f;  // the weight (and its divisor) join the row here, after the loads: they hold
+                                     // no register across them
+                    if constexpr (WM != 0) wu = __shfl(wf, j + u < m ? j + u : j, G);
+                    if constexpr (WM == 1) c[u] = __shfl(cf, j + u < m ? j + u : j, G);
+                    const float r = (OP == GS_AGG_MEAN && WM != 2 && GS_FULL_BWD_QUOT_MODE != 0) ? 1.0f / c[u] : 0.f;
 #pragma unroll
                     for (int v = 0; v < VEC; ++v) {
-                        if constexpr (OP == GS_AGG_MEAN) acc[v] += ok[u] ? mean_quot(x[u][v], c[u], r) : 0.f;
+                        if constexpr (WM == 1) acc[v] = fmaf(wu, ok[u] ? mean_quot(x[u][v], c[u], r) : 0.f, acc[v]);
+                        else if constexpr (WM == 2) acc[v] = fmaf(wu, ok[u] ? x[u][v] : 0.f, acc[v]);
+                        else if constexpr (OP == GS_AGG_MEAN) acc[v] += ok[u] ? mean_quot(x[u][v], c[u], r) : 0.f;
                         else acc[v] += (ok[u] && id[u][v] == node) ? x[u][v] : 0.f;
                     }
                 }
@@ -369,8 +389,24 @@ template <int OP>
 void launch_bwd_t(bool vec, const BwdArgs& a, hipStream_t st) {
     with_group<4>(vec, a.F, [&](auto vc, auto gc) {
         constexpr int VEC = decltype(vc)::value, G = decltype(gc)::value;
-        launch_walk_combine<G>(a.pos != nullptr, a.n_items, a.n_split, st, agg_full_bwd_kernel<OP, VEC, G, true>,
-                               agg_full_bwd_combine_kernel<VEC, G, true>, agg_full_bwd_kernel<OP, VEC, G, false>,
+        if constexpr (OP == GS_AGG_MEAN) {
+            if (a.w && a.den) {
+                launch_walk_combine<G>(a.pos != nullptr, a.n_items, a.n_split, st,
+                                       agg_full_bwd_kernel<OP, VEC, G, true, 1>, agg_full_bwd_combine_kernel<VEC, G, true>,
+                                       agg_full_bwd_kernel<OP, VEC, G, false, 1>,
+                                       agg_full_bwd_combine_kernel<VEC, G, false>, a);
+                return;
+            }
+            if (a.w) {
+                launch_walk_combine<G>(a.pos != nullptr, a.n_items, a.n_split, st,
+                                       agg_full_bwd_kernel<OP, VEC, G, true, 2>, agg_full_bwd_combine_kernel<VEC, G, true>,
+                                       agg_full_bwd_kernel<OP, VEC, G, false, 2>,
+                                       agg_full_bwd_combine_kernel<VEC, G, false>, a);
+                return;
+            }
+        }
+        launch_walk_combine<G>(a.pos != nullptr, a.n_items, a.n_split, st, agg_full_bwd_kernel<OP, VEC, G, true, 0>,
+                               agg_full_bwd_combine_kernel<VEC, G, true>, agg_full_bwd_kernel<OP, VEC, G, false, 0>,
                                agg_full_bwd_combine_kernel<VEC, G, false>, a);
     });
 }
@@ -386,6 +422,7 @@ void agg_full_argmax_launch(const FullPlan& p, const gs_full_plan_dev& d, gs_dty
                             void* out, int64_t ldo, int32_t* argmax, int64_t lda, void* ws, int64_t ws_bytes,
                             hipStream_t st, const FieldLayer* fl) {
     GS_REQUIRE(dt == GS_F32, GS_EINVAL, "gs_agg_full_argmax: fp32 rows only (a bf16 table's aggregate has no backward)");
+    GS_REQUIRE(!d.weight, GS_EINVAL, "gs_agg_full_argmax: edge weights go with MEAN, not MAX");
     GS_REQUIRE(!p.transposed, GS_EINVAL, "gs_agg_full_argmax: a forward plan expected");
     const int64_t need = agg_full_argmax_ws_need(p, F, row0, n_rows);
     GS_REQUIRE(ldx >= F && ldo >= F && lda >= F, GS_EINVAL, "leading dimension smaller than F");
@@ -424,6 +461,8 @@ void agg_full_bwd_launch(const FullPlan& tp, const gs_full_plan_dev& td, gs_agg 
                          int64_t ldd, const int32_t* argmax, int64_t lda, const float* Hprev, float* dH, int64_t ldh,
                          void* ws, int64_t ws_bytes, hipStream_t st, const FieldLayer* fl, int64_t ldo) {
     GS_REQUIRE(op == GS_AGG_MEAN || op == GS_AGG_MAX, GS_EINVAL, "agg_func must be MEAN or MAX");
+    GS_REQUIRE(op != GS_AGG_MAX || !td.weight, GS_EINVAL, "edge weights go with MEAN, not MAX");
+    GS_REQUIRE(td.weight || !td.denom, GS_EINVAL, "denom without weight");
     const int64_t need = agg_full_bwd_ws_need(tp, F);
     GS_REQUIRE(!fl || ldo >= F, GS_EINVAL, "leading dimension smaller than F");
     GS_REQUIRE(ldd >= F && ldh >= F && (op != GS_AGG_MAX || lda >= F), GS_EINVAL, "leading dimension smaller than F");
@@ -443,6 +482,8 @@ void agg_full_bwd_launch(const FullPlan& tp, const gs_full_plan_dev& td, gs_agg 
     a.slot_ptr = td.slot_ptr;
     a.split_rows = td.split_rows;
     a.cnt = td.count;
+    a.w = td.weight;
+    a.den = td.denom;
     a.dA = dA;
     a.dSelf = dSelf;
     a.ldd = ldd;

@@ -67,6 +67,7 @@ void infer_full_run(const FullPlan& p, const gs_full_plan_dev& d, const gs_infer
     for (int l = 0; l < L; ++l) GS_REQUIRE(c.W[l], GS_EINVAL, "NULL weight");
     GS_REQUIRE(ws && ws_bytes >= lo.total && (reinterpret_cast<uintptr_t>(ws) & (kAlign - 1)) == 0, GS_EINVAL,
                "workspace smaller than gs_infer_full_ws_bytes or not 256-byte aligned");
+    GS_REQUIRE(c.agg != GS_AGG_MAX || !d.weight, GS_EINVAL, "edge weights go with MEAN, not MAX");
     if (c.agg == GS_AGG_MAX && !p.empty_rows.empty())
         fail(GS_EEMPTY, "gs_infer_full: MAX aggregation over an empty neighbourhood (reference: models.py:321-325)");
     char* base = static_cast<char*>(ws);

@@ -223,6 +223,9 @@ void train_full_run(const FullPlan& p, const gs_full_plan_dev& d, const FullPlan
             "workspace smaller than gs_train_full_ws_bytes or not 256-byte aligned");
     require(aligned16(c.params) && aligned16(c.grads), "params / grads must be 16-byte aligned");
     require(!f || f->n_layers == L, "the field was built for another number of layers");
+    require(c.agg != GS_AGG_MAX || (!d.weight && !td.weight), "edge weights go with MEAN, not MAX");
+    require(!d.weight == !td.weight && !d.denom == !td.denom,
+            "the forward and the transposed plan must carry the same edge-weight set");
     if (!p.empty_rows.empty())
         fail(GS_EEMPTY, "gs_train_full: a node's effective neighbourhood is empty (reference: models.py:313, :321-325)");
     FieldLayer fl[GS_MAX_HOPS + 1];

@@ -78,7 +78,7 @@ class FullPlan:
     _DTYPES = {_lib.GS_FP_ITEMS: "int32", _lib.GS_FP_ITEM_PTR: "int64", _lib.GS_FP_SLOT_PTR: "int64",
                _lib.GS_FP_SPLIT_PTR: "int64", _lib.GS_FP_SPLIT_ROWS: "int32", _lib.GS_FP_COUNT: "int32",
                _lib.GS_FP_SELF_LOOP: "uint8", _lib.GS_FP_EMPTY_ROWS: "int32", _lib.GS_FP_T_ROW_PTR: "int64",
-               _lib.GS_FP_T_COL: "int32"}
+               _lib.GS_FP_T_COL: "int32", _lib.GS_FP_T_SRC: "int64"}
     is_transposed = False
 
     def __init__(self, graph, gcn=False, seg_len=None):
@@ -123,8 +123,12 @@ class FullPlan:
         neighbourhood (this plan's gcn rule) holds u, ascending -- cut into
         segments of its own.  Its row_ptr / col are that CSR, and its
         COUNT array is this plan's (the MEAN divisor of every destination).
+        Its T_SRC array names, for every transposed entry, the entry of this
+        plan's col it came from (-1: the self entry gcn added), which is how
+        EdgeWeights carries per-edge weights over.
         Correct for directed input: symmetry is never assumed."""
         import ctypes
+        import weakref
         if self.is_transposed:
             raise ValueError("FullPlan.transposed: the plan is already a transposed one")
         seg_len = self.seg_len if seg_len is None else int(seg_len)
@@ -133,6 +137,7 @@ class FullPlan:
             check(lib().gs_full_plan_transpose(self._h, ptr(self.row_ptr), ptr(self.col), seg_len, ctypes.byref(h)))
             t = FullPlan.__new__(FullPlan)
             t._h, t._t, t.graph, t.is_transposed = h, {}, None, True
+            t._fwd = weakref.ref(self)
             t._read_dims()
             t.row_ptr = t.array(_lib.GS_FP_T_ROW_PTR)
             t.col = t.array(_lib.GS_FP_T_COL)
@@ -148,7 +153,8 @@ class FullPlan:
              _lib.GS_FP_SLOT_PTR: self.n_nodes + 1, _lib.GS_FP_SPLIT_PTR: self.n_nodes + 1,
              _lib.GS_FP_SPLIT_ROWS: self.n_split, _lib.GS_FP_COUNT: self.n_nodes,
              _lib.GS_FP_SELF_LOOP: self.n_nodes, _lib.GS_FP_EMPTY_ROWS: self.n_empty,
-             _lib.GS_FP_T_ROW_PTR: self.n_nodes + 1, _lib.GS_FP_T_COL: self.n_entries}[which]
+             _lib.GS_FP_T_ROW_PTR: self.n_nodes + 1, _lib.GS_FP_T_COL: self.n_entries,
+             _lib.GS_FP_T_SRC: self.n_entries}[which]
         dt = np.dtype(self._DTYPES[which])
         if n == 0:
             return np.zeros(0, dt)
@@ -191,7 +197,7 @@ class FullPlan:
 
 
 def agg_full(agg_func, X, graph, out=None, *, gcn=False, seg_len=None, row0=0, n_rows=None, ws=None, argmax=None,
-             field=None, layer=None):
+             field=None, layer=None, edge_weight=None):
     """Full-neighbourhood mean/max of rows of X over the device CSR for the
     destination rows [row0, row0 + n_rows) (gs_agg_full): adj[v] without v, or
     with v exactly once under gcn; rows longer than `seg_len` entries are
@@ -207,10 +213,14 @@ def agg_full(agg_func, X, graph, out=None, *, gcn=False, seg_len=None, row0=0, n
     `field`, `layer` (a ReceptiveField of this plan, 1 <= layer <= its depth):
     only the rows of R_layer, row v as row field.pos(layer)[v] of a compact
     [n_layer, F] out (and argmax, which still holds global source ids); every
-    row is bitwise the unrestricted call's (gs_agg_full_field)."""
+    row is bitwise the unrestricted call's (gs_agg_full_field).
+    `edge_weight` (an EdgeWeights of this plan, MEAN only): the weighted mean
+    or sum it describes, with a window and with a field alike; with unit
+    weights and norm="mean" the result is bitwise the unweighted one."""
     _dev(X, out, ws, argmax)
     import ctypes
     plan = graph if isinstance(graph, FullPlan) else agg_full_plan(graph, gcn=gcn, seg_len=seg_len)
+    _check_edge_weight("agg_full", edge_weight, plan, agg_func)
     if field is not None:
         if field.plan is not plan or not field.build_id:
             raise ValueError("agg_full: the field was built for another plan (or not built)")
@@ -242,6 +252,8 @@ def agg_full(agg_func, X, graph, out=None, *, gcn=False, seg_len=None, row0=0, n
     if ws is None:
         ws = torch.empty(max(need, 16), dtype=torch.uint8, device=X.device)
     d, rp, cl = plan.device(X.device)
+    if edge_weight is not None:
+        d = edge_weight.device(X.device)
     if argmax is not None:
         if argmax.dtype != torch.int32 or argmax.dim() != 2 or argmax.stride(1) != 1 or argmax.shape[0] < n_rows or \
                 argmax.shape[1] < F:
@@ -281,7 +293,7 @@ def agg_full_bwd_plan(graph, *, gcn=False, seg_len=None):
 
 
 def agg_full_bwd(agg_func, dA, graph, dH=None, *, gcn=False, seg_len=None, dSelf=None, argmax=None, Hprev=None,
-                 ws=None, field=None, layer=None):
+                 ws=None, field=None, layer=None, edge_weight=None):
     """Backward of agg_full over all rows (gs_agg_full_bwd), fp32:
     dH[u] = sum over the destinations v that read u of dA[v] / count[v] (MEAN)
     or of dA[v] where argmax[v] == u (MAX; `argmax` from agg_full), plus
@@ -293,7 +305,10 @@ def agg_full_bwd(agg_func, dA, graph, dH=None, *, gcn=False, seg_len=None, dSelf
     (gs_agg_full_bwd_field).  dA, dSelf and argmax are then compact in R_layer
     order ([n_layer, F]; destinations outside R_layer are skipped, dSelf is
     added only where u is in R_layer), Hprev stays the [n_nodes, F] table,
-    and dH is compact in R_{layer-1} order ([n_{layer-1}, F])."""
+    and dH is compact in R_{layer-1} order ([n_{layer-1}, F]).
+    `edge_weight` (the EdgeWeights the forward ran with, MEAN only):
+    dH[u] = sum of w_vu dA[v] / den[v] (norm="mean") or of w_vu dA[v]
+    (norm="sum"); the weights themselves take no gradient."""
     _dev(dA, dH, dSelf, argmax, Hprev, ws)
     import ctypes
     if field is not None:
@@ -315,6 +330,7 @@ def agg_full_bwd(agg_func, dA, graph, dH=None, *, gcn=False, seg_len=None, dSelf
         na = nh = nd = tplan.n_nodes
         ra = rd = "n_nodes"
     op = agg_op(agg_func)
+    _check_edge_weight("agg_full_bwd", edge_weight, tplan._fwd(), agg_func)
 
     def ok(t, rows, width=0, dtype=torch.float32):
         return t.dtype == dtype and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] == rows and t.shape[1] >= width
@@ -340,6 +356,8 @@ def agg_full_bwd(agg_func, dA, graph, dH=None, *, gcn=False, seg_len=None, dSelf
     if ws is None:
         ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dA.device)
     d, rp, cl = tplan.device(dA.device)
+    if edge_weight is not None:
+        d = edge_weight.t_device(tplan, dA.device)
     lda = argmax.stride(0) if argmax is not None else 0
     if field is None:
         check(lib().gs_agg_full_bwd(tplan.handle, ctypes.byref(d), op, F, ptr(rp), ptr(cl), ptr(dA), ptr(dSelf),
@@ -351,6 +369,199 @@ def agg_full_bwd(agg_func, dA, graph, dH=None, *, gcn=False, seg_len=None, dSelf
                                           ptr(Hprev), Hprev.stride(0) if Hprev is not None else 0, ptr(dH),
                                           dH.stride(0), ptr(ws), ws.numel() * ws.element_size(), _stream(dA)))
     return dH
+
+
+# ------------------------------------------------- per-edge weights of the exact path
+def _check_edge_weight(who, ew, plan, agg_func):
+    """Every refusal of an `edge_weight=` argument, before any launch."""
+    if ew is None:
+        return
+    if not isinstance(ew, EdgeWeights):
+        raise TypeError(f"{who}: edge_weight must be a hip_ops.EdgeWeights")
+    if ew.plan is not plan:
+        raise ValueError(f"{who}: the edge weights were made for another plan (graph, gcn or seg_len)")
+    if agg_op(agg_func) == _lib.GS_AGG_MAX:
+        raise ValueError(f"{who}: edge weights go with MEAN; MAX selects and has no weighted form")
+
+
+class EdgeWeights:
+    """Per-edge weights of a forward FullPlan, for `edge_weight=` of agg_full /
+    agg_full_bwd and for FullEmbedder / FullTrainer.
+
+    `w`: float32 [n_entries], aligned with the plan's CSR `col` (entry e of
+    row v weighs X[col[e]] in out[v]; edge_weights_from_pairs maps (dst, src,
+    w) triples onto that order).  The effective entries of a row are the
+    unweighted kernel's: without gcn an entry equal to the row's own id is
+    skipped and its weight ignored; with gcn every entry counts with its own
+    weight and a row without a self entry gets one last, weighing
+    `self_weight[v]` (a scalar or [n_nodes]).
+        S[v] = sum over eff(v) of fmaf(w_e, X[col_e], acc)   fp32, the unweighted visiting order
+        norm="sum":  out[v] = S[v]
+        norm="mean": out[v] = S[v] / den[v],  den[v] = sum over eff(v) of w_e
+    den is computed here, once per weight set, on the host: summed in float64
+    per row in entry order and rounded to fp32 (no floating-point atomics), so
+    with unit weights it is float(count[v]) and the weighted mean is bitwise
+    the unweighted one.  Weights must be finite; negative and zero weights are
+    allowed (a zero-weight edge is still an edge of the receptive field), and
+    a row whose den is 0 gets what IEEE gives.  The weights are data: there is
+    no gradient with respect to them.
+
+    The backward reads the weights in the transposed plan's entry order: w is
+    permuted through the transposed plan's T_SRC array (-1, the self entry gcn
+    added, takes self_weight), once -- the transposed CSR's entry order does
+    not depend on its seg_len.  device() / t_device() hand out weighted COPIES
+    of the plans' device structs; the plans' own (unweighted, shared per
+    graph) structs are never touched.  host(): (w, den, w_t) as numpy."""
+
+    def __init__(self, plan, w, norm="mean", self_weight=1.0):
+        import numpy as np
+        if not isinstance(plan, FullPlan) or plan.is_transposed:
+            raise ValueError("EdgeWeights: a forward FullPlan expected")
+        if norm not in ("mean", "sum"):
+            raise ValueError("EdgeWeights: norm must be 'mean' or 'sum'")
+        self.plan, self.norm = plan, norm
+        self.w = self._values(w, plan.n_entries, "w must hold one weight per CSR entry (n_entries)")
+        sw = self_weight.detach().cpu().numpy() if isinstance(self_weight, torch.Tensor) else np.asarray(self_weight)
+        if sw.ndim == 0:
+            sw = np.full(plan.n_nodes, float(sw), np.float32)
+        self.self_weight = self._values(sw, plan.n_nodes, "self_weight must be a scalar or hold n_nodes values")
+        self.den = np.zeros(plan.n_nodes, np.float32)
+        if plan.n_nodes:
+            check(lib().gs_full_plan_edge_denom(plan.handle, ptr(plan.row_ptr), ptr(plan.col), ptr(self.w),
+                                                ptr(self.self_weight), ptr(self.den)))
+        self._w_t = None
+        self._dev = {}
+
+    @staticmethod
+    def _values(a, n, msg):
+        import numpy as np
+        if isinstance(a, torch.Tensor):
+            a = a.detach().cpu().numpy()
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.ndim != 1 or len(a) != n:
+            raise ValueError("EdgeWeights: " + msg)
+        if not np.isfinite(a).all():
+            raise ValueError("EdgeWeights: weights must be finite")
+        return a
+
+    def bad_rows(self):
+        """Rows whose den is not finite and > 0: what norm="mean" cannot divide by."""
+        import numpy as np
+        return np.nonzero(~(np.isfinite(self.den) & (self.den > 0)))[0]
+
+    def transposed_weights(self):
+        """w in the transposed CSR's entry order (float32 [t_entries])."""
+        import numpy as np
+        if self._w_t is None:
+            ts = self.plan._t
+            t = next(iter(ts.values())) if ts else self.plan.transposed()
+            src = t.array(_lib.GS_FP_T_SRC)
+            w_t = np.empty(len(src), np.float32)
+            fwd = src >= 0
+            w_t[fwd] = self.w[src[fwd]]
+            w_t[~fwd] = self.self_weight[t.col[~fwd]]  # gcn's added self entry: row u's own, t_col == u
+            self._w_t = w_t
+        return self._w_t
+
+    def host(self):
+        """(w, den, w_t) as numpy arrays: forward order, per destination, transposed order."""
+        return self.w, self.den, self.transposed_weights()
+
+    def _tensors(self, device):
+        key = str(torch.device(device))
+        if key not in self._dev:
+            def up(a):  # an empty array still gets an address
+                return torch.from_numpy(a).to(device) if len(a) else torch.zeros(1, device=device)
+
+            self._dev[key] ={"w": up(self.w), "den": up(self.den), "sw": up(self.self_weight), "structs": {}}
+        return self._dev[key]
+
+    def _struct(self, plan, device, weight, self_weight):
+        ts = self._tensors(device)
+        if id(plan) not in ts["structs"]:
+            base = plan.device(device)[0]
+            d = _lib.FullPlanDev(items=base.items, slot_ptr=base.slot_ptr, split_rows=base.split_rows,
+                                 count=base.count, self_loop=base.self_loop, weight=ptr(weight),
+                                 denom=ptr(ts["den"]) if self.norm == "mean" else None,
+                                 self_weight=ptr(self_weight) if self_weight is not None else None)
+            ts["structs"][id(plan)] = (d, plan)
+        return ts["structs"][id(plan)][0]
+
+    def device(self, device):
+        """The forward plan's gs_full_plan_dev with this weight set; the tensors stay alive with this object."""
+        ts = self._tensors(device)
+        return self._struct(self.plan, device, ts["w"], ts["sw"])
+
+    def t_device(self, tplan, device):
+        """A transposed plan's gs_full_plan_dev with this weight set (weights in its entry order)."""
+        if not isinstance(tplan, FullPlan) or not tplan.is_transposed or tplan._fwd() is not self.plan:
+            raise ValueError("EdgeWeights: a transposed plan of this weight set's forward plan expected")
+        ts = self._tensors(device)
+        if "w_t" not in ts:
+            w_t = self.transposed_weights()
+            ts["w_t"] = torch.from_numpy(w_t).to(device) if len(w_t) else torch.zeros(1, device=device)
+        return self._struct(tplan, device, ts["w_t"], None)
+
+
+def edge_weights_from_pairs(row_ptr, col, dst, src, w, symmetric=False, default=None):
+    """float32 [n_entries] weights in the CSR's entry order from weighted edge
+    triples: entry e of row v with col[e] == u takes the weight of the triple
+    (dst = v, src = u), looked up by the key dst * n + src (a CSRGraph's rows
+    are in CPython-set order, which no caller can guess).  `symmetric`: every
+    triple also stands for (src, dst).  A CSR entry without a triple raises
+    KeyError unless `default` is given; a triple given twice (after
+    `symmetric` mirrored them) raises ValueError; a triple without a CSR entry
+    is ignored."""
+    import numpy as np
+    row_ptr = np.asarray(row_ptr, np.int64)
+    col = np.asarray(col, np.int64)
+    n = len(row_ptr) - 1
+    dst = np.asarray(dst, np.int64).reshape(-1)
+    src = np.asarray(src, np.int64).reshape(-1)
+    w = np.asarray(w, np.float32).reshape(-1)
+    if not (len(dst) == len(src) == len(w)):
+        raise ValueError("edge_weights_from_pairs: dst, src and w must have one length")
+    if len(dst) and (min(dst.min(), src.min()) < 0 or max(dst.max(), src.max()) >= n):
+        raise IndexError("edge_weights_from_pairs: node id out of range")
+    if symmetric:
+        off = dst != src
+        dst, src, w = np.concatenate([dst, src[off]]), np.concatenate([src, dst[off]]), np.concatenate([w, w[off]])
+    keys = dst * n + src
+    order = np.argsort(keys, kind="stable")
+    keys, w = keys[order], w[order]
+    if len(keys) > 1 and (keys[1:] == keys[:-1]).any():
+        k = int(keys[1:][keys[1:] == keys[:-1]][0])
+        raise ValueError(f"edge_weights_from_pairs: the edge (dst {k // n}, src {k % n}) is given twice")
+    n_entries = int(row_ptr[-1])
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(row_ptr))
+    want = rows * n + col[:n_entries]
+    at = np.searchsorted(keys, want)
+    hit = at < len(keys)
+    hit[hit] = keys[at[hit]] == want[hit]
+    if default is None and not hit.all():
+        k = int(want[~hit][0])
+        raise KeyError(f"edge_weights_from_pairs: no weight for the CSR entry (dst {k // n}, src {k % n})")
+    out = np.full(n_entries, 0.0 if default is None else default, np.float32)
+    out[hit] = w[at[hit]]
+    return out
+
+
+def sym_norm_weights(plan):
+    """(w float32 [n_entries], self_weight float32 [n_nodes]) of the Kipf-Welling
+    symmetric normalisation over a forward FullPlan: w_e = 1 / sqrt(c_v c_u)
+    for entry e = (v reads u) and self_weight[v] = 1 / c_v, with c the plan's
+    effective counts.  They go with norm="sum"; under gcn that aggregate is
+    D^-1/2 (A + I) D^-1/2 X.  A node that is read but has no effective entry
+    of its own (c = 0) gives an infinite weight, which EdgeWeights refuses."""
+    import numpy as np
+    if not isinstance(plan, FullPlan) or plan.is_transposed:
+        raise ValueError("sym_norm_weights: a forward FullPlan expected")
+    c = plan.array(_lib.GS_FP_COUNT).astype(np.float64)
+    rows = np.repeat(np.arange(plan.n_nodes, dtype=np.int64), np.diff(plan.row_ptr))
+    with np.errstate(divide="ignore"):
+        w = 1.0 / np.sqrt(c[rows] * c[plan.col[:plan.n_entries]])
+        sw = 1.0 / c
+    return w.astype(np.float32), sw.astype(np.float32)
 
 
 # ------------------------------------------------- the receptive field of a batch

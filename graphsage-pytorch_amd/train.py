@@ -625,15 +625,19 @@ class FullEmbedder:
     the reference's 0/0; MAX raises IndexError here, at construction, when any
     node's neighbourhood is empty (as Embedder does when it samples one).
     `seg_len` / `chunk_rows`: None takes the measured defaults
-    (hip_ops.FULL_SEG_LEN, FULL_CHUNK_ROWS).  Single GPU, inference only."""
+    (hip_ops.FULL_SEG_LEN, FULL_CHUNK_ROWS).  `edge_weight`, `edge_norm`,
+    `self_weight`: per-edge weights, as FullTrainer takes them (MEAN only; not
+    a reference feature).  Single GPU, inference only."""
 
-    def __init__(self, graph, features, weights, agg_func="MEAN", gcn=False, seg_len=None, chunk_rows=None):
+    def __init__(self, graph, features, weights, agg_func="MEAN", gcn=False, seg_len=None, chunk_rows=None,
+                 edge_weight=None, edge_norm="mean", self_weight=1.0):
         self.agg, self.gcn = agg_func, bool(gcn)
         op = ops.agg_op(agg_func)
         self.plan = ops.agg_full_plan(graph, gcn=gcn, seg_len=seg_len)
         if agg_func == "MAX" and self.plan.n_empty:
             raise IndexError(f"MAX aggregation over an empty neighbourhood ({self.plan.n_empty} nodes have none; "
                              "reference: models.py:321-325)")
+        self.edge_weights = _edge_weights("FullEmbedder", self.plan, agg_func, edge_weight, edge_norm, self_weight)
         if not features.is_cuda:
             raise RuntimeError("FullEmbedder runs on a HIP device")
         if features.dim() != 2 or features.stride(1) != 1 or features.shape[0] != graph.n_nodes or \
@@ -648,6 +652,8 @@ class FullEmbedder:
                 raise ValueError(f"weights[{l}] must be [{self.H}, {m * (F if l == 0 else self.H)}]")
         self.chunk_rows = ops.FULL_CHUNK_ROWS if chunk_rows is None else int(chunk_rows)
         self._dev, self.row_ptr, self.col = self.plan.device(self.device)
+        if self.edge_weights is not None:
+            self._dev = self.edge_weights.device(self.device)
         self.cfg = _lib.InferFullConfig(
             n_layers=self.L, hidden=self.H, agg=op,
             feat_dtype=_lib.GS_BF16 if features.dtype == torch.bfloat16 else _lib.GS_F32, feat_dim=F,
@@ -673,6 +679,34 @@ class FullEmbedder:
             return out
         idx = torch.from_numpy(np.ascontiguousarray(nodes, dtype=np.int64).reshape(-1)).to(self.device)
         return out.index_select(0, idx)
+
+
+def _edge_weights(who, plan, agg_func, edge_weight, edge_norm, self_weight):
+    """The hip_ops.EdgeWeights of an exact embedder or trainer (None: unweighted), every refusal at construction:
+    `edge_weight` is None, per-entry values (numpy or torch, the CSR's col order), "sym" (hip_ops.sym_norm_weights
+    with norm="sum") or an EdgeWeights of this very plan."""
+    if edge_weight is None:
+        return None
+    if agg_func == "MAX":
+        raise ValueError(f"{who}: edge weights go with agg_func='MEAN'; MAX selects and has no weighted form")
+    if isinstance(edge_weight, ops.EdgeWeights):
+        if edge_weight.plan is not plan:
+            raise ValueError(f"{who}: the edge weights were made for another plan (graph, gcn or seg_len)")
+        ew = edge_weight
+    elif isinstance(edge_weight, str):
+        if edge_weight != "sym":
+            raise ValueError(f"{who}: edge_weight must be per-entry values, an EdgeWeights or 'sym'")
+        w, sw = ops.sym_norm_weights(plan)
+        ew = ops.EdgeWeights(plan, w, norm="sum", self_weight=sw)
+    else:
+        ew = ops.EdgeWeights(plan, edge_weight, norm=edge_norm, self_weight=self_weight)
+    if ew.norm == "mean":
+        bad = ew.bad_rows()
+        if len(bad):
+            raise ValueError(f"{who}: under edge_norm='mean' {len(bad)} rows have a weight sum that is not finite and "
+                             f"> 0 (the first: node {int(bad[0])}), whose mean is a NaN or infinite row; use "
+                             "edge_norm='sum' or other weights")
+    return ew
 
 
 # ------------------------------------------------------- full-batch training
@@ -897,11 +931,26 @@ class FullTrainer:
     Runner, the GraphSage / Classification modules), ClassifierProbe, soft
     targets.
 
+    Per-edge weights (not a reference feature; MEAN only, ValueError under
+    MAX): `edge_weight` is float32 [n_entries] in the CSR's col order
+    (hip_ops.edge_weights_from_pairs maps (dst, src, w) triples onto it), a
+    hip_ops.EdgeWeights of this trainer's plan, or "sym" -- Kipf-Welling's
+    1 / sqrt(c_v c_u) with edge_norm="sum", under gcn D^-1/2 (A + I) D^-1/2.
+    edge_norm="mean" divides a row's weighted sum by the sum of its weights,
+    "sum" leaves it; `self_weight` (a scalar or [N]) weighs the self row gcn
+    appends.  Every aggregate of the step, forward and backward, full, with
+    `field=` and with `unsup=`, in embed and in evaluate, then runs weighted;
+    with unit weights the step is bitwise the unweighted one.  The weights are
+    data and take no gradient.  Under "mean" a row whose weight sum is not
+    finite and > 0 is refused at construction, as an empty row is.
+    set_edge_weight swaps the weight set between steps.
+
     Single GPU.  Out of scope: data parallel."""
 
     def __init__(self, graph, features, labels, n_classes, num_layers=2, hidden=128, agg_func="MEAN", gcn=False,
                  lr=0.7, max_norm=5.0, seed=824, weights=None, optimizer="sgd", betas=(0.9, 0.999), eps=1e-8,
-                 weight_decay=0.0, seg_len=None, cache_agg1=True, head="nll", pos_weight=None):
+                 weight_decay=0.0, seg_len=None, cache_agg1=True, head="nll", pos_weight=None, edge_weight=None,
+                 edge_norm="mean", self_weight=1.0):
         if head not in ("nll", "multilabel"):
             raise ValueError("FullTrainer: head must be 'nll' or 'multilabel'")
         self.head = head
@@ -917,6 +966,7 @@ class FullTrainer:
                                  "reference: models.py:321-325)")
             raise ValueError(f"FullTrainer: {self.plan.n_empty} nodes have an empty neighbourhood, whose MEAN is a "
                              "NaN row in every loss; use gcn=True or train on a self-contained subgraph")
+        self.edge_weights = _edge_weights("FullTrainer", self.plan, agg_func, edge_weight, edge_norm, self_weight)
         if not features.is_cuda:
             raise RuntimeError("FullTrainer runs on a HIP device")
         if features.dim() != 2 or features.stride(1) != 1 or features.shape[0] != graph.n_nodes or \
@@ -965,6 +1015,9 @@ class FullTrainer:
         self.tplan = self.plan.transposed(ops.FULL_BWD_SEG_LEN if seg_len is None else seg_len)
         self._dev, self.row_ptr, self.col = self.plan.device(self.device)
         self._tdev, self.t_row_ptr, self.t_col = self.tplan.device(self.device)
+        if self.edge_weights is not None:
+            self._dev = self.edge_weights.device(self.device)
+            self._tdev = self.edge_weights.t_device(self.tplan, self.device)
         self._loss3 = torch.zeros(3, dtype=torch.float32, device=self.device)  # total, loss_sup, loss_net
         self.loss = self._loss3[:1]
         self._uws = None           # the unsupervised head's buffer: grows on demand, kept between batches
@@ -1026,6 +1079,26 @@ class FullTrainer:
         """Recompute layer 1's aggregate on the next step, full or restricted (the feature table changed in
         place)."""
         self._agg1 = None
+
+    def set_edge_weight(self, edge_weight, edge_norm="mean", self_weight=1.0):
+        """Replace the weight set (the constructor's three arguments; None: back to unweighted) between steps.
+        No plan is rebuilt; layer 1's cached aggregate and embed()'s embedder are dropped, so the next step,
+        embed and evaluate are those of a trainer constructed with these weights.  The launches already issued
+        keep the old set, which stays alive until the next call."""
+        ew = _edge_weights("FullTrainer", self.plan, self.agg, edge_weight, edge_norm, self_weight)
+        self._old_edge_weights, self.edge_weights = self.edge_weights, ew
+        if ew is None:
+            self._dev, self._tdev = self.plan.device(self.device)[0], self.tplan.device(self.device)[0]
+        else:
+            self._dev, self._tdev = ew.device(self.device), ew.t_device(self.tplan, self.device)
+        self._agg1 = None
+        self._embedder = None
+
+    def _embedder_weights(self):
+        """The weight arguments of embed()'s FullEmbedder: this trainer's set, by value (its plan is looked up
+        again there)."""
+        ew = self.edge_weights
+        return {} if ew is None else {"edge_weight": ew.w, "edge_norm": ew.norm, "self_weight": ew.self_weight}
 
     def field(self, nodes, out=None):
         """The receptive field of `nodes` under this trainer's plans and depth
@@ -1265,7 +1338,7 @@ class FullTrainer:
             return self.hidden().index_select(0, nodes.long())
         if self._embedder is None:
             self._embedder = FullEmbedder(self.graph, self.X, self.weights(), agg_func=self.agg, gcn=self.gcn,
-                                          seg_len=self.plan.seg_len)
+                                          seg_len=self.plan.seg_len, **self._embedder_weights())
         for dst, src in zip(self._embedder.W, self.weights()):
             dst.copy_(src)
         return self._embedder.embed(nodes)

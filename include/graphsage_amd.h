@@ -1043,14 +1043,48 @@ enum { GS_FP_ITEMS = 0, GS_FP_ITEM_PTR, GS_FP_SLOT_PTR, GS_FP_SPLIT_PTR, GS_FP_S
        GS_FP_COUNT, GS_FP_SELF_LOOP, GS_FP_EMPTY_ROWS };
 const void* gs_full_plan_array(const gs_full_plan* plan, int32_t which);
 
-/* Device copies of the arrays the kernels read (uploaded by the caller). */
+/* Device copies of the arrays the kernels read (uploaded by the caller).
+ *
+ * Per-edge weights (MEAN only) ride in the three trailing members; all NULL
+ * (a zero-initialised struct) is the unweighted aggregate.
+ *   weight       fp32, one per entry in the plan's OWN entry order: the CSR's
+ *                col order for a forward plan, the transposed CSR's for a
+ *                transposed one (forward weights permuted through GS_FP_T_SRC,
+ *                a -1 entry taking self_weight of its row).  Finite values;
+ *                negative and zero weights are fine.
+ *   denom        fp32 [n], indexed by DESTINATION in both plans: the divisor
+ *                of the weighted mean, the sum of the weights of the row's
+ *                effective entries (summed in double in entry order, rounded
+ *                once; float(COUNT) for unit weights).  NULL: the weighted sum,
+ *                no division.  Set only together with weight.
+ *   self_weight  fp32 [n]: the weight of the self row gcn appends to a row
+ *                without a self loop (read only there, forward plans only;
+ *                NULL: 1).  Entries equal to the row's own id are skipped
+ *                without gcn, whatever their weight, and count with their own
+ *                weight under gcn.
+ * Forward: out[v] = sum_e fmaf(w_e, X[col_e], acc) in the unweighted visiting
+ * order (/ denom[v]); backward: dH[u] = sum fmaf(w_vu, dA[v] (/ denom[v]), acc).
+ * With unit weights and denom = float(COUNT) both are bitwise the unweighted
+ * results.  Every MAX call with weight set is GS_EINVAL. */
 typedef struct {
     const int32_t* items;
     const int64_t* slot_ptr;
     const int32_t* split_rows;
     const int32_t* count;
     const uint8_t* self_loop;
+    const float* weight;
+    const float* denom;
+    const float* self_weight;
 } gs_full_plan_dev;
+
+/* The weighted mean's divisor (gs_full_plan_dev.denom) on the host, for a
+ * forward plan and its CSR: den[v] = the sum of w[e] over the row's effective
+ * entries (entries equal to v are left out without gcn; under gcn every entry
+ * counts and a row without a self loop adds self_weight[v], 1 when NULL),
+ * accumulated in double in entry order and rounded to fp32 once.  No atomics
+ * and no device pass: with unit weights it is float(COUNT[v]) exactly. */
+int gs_full_plan_edge_denom(const gs_full_plan* plan, const int64_t* row_ptr, const int32_t* col,
+                            const float* w, const float* self_weight, float* den);
 
 /* Full-neighbourhood aggregate of destination rows [row0, row0 + n_rows):
  *   out[v - row0] = MEAN / MAX of X[u] over u in adj[v] \ {v}  (gcn: U {v},
@@ -1104,8 +1138,14 @@ int gs_infer_full(const gs_full_plan* plan, const gs_full_plan_dev* dev, const g
  * owns the CSR (arrays GS_FP_T_ROW_PTR int64 [n + 1] and GS_FP_T_COL int32
  * [n_entries]; NULL for a forward plan); its COUNT array is the forward
  * plan's, the MEAN divisor of each destination.  (row_ptr, col) must be the
- * host CSR the forward plan was built from. */
-enum { GS_FP_T_ROW_PTR = 8, GS_FP_T_COL = 9 };
+ * host CSR the forward plan was built from.
+ * GS_FP_T_SRC int64 [n_entries of the transposed CSR]: the index into the
+ * forward col of the entry each transposed entry came from, filled in the same
+ * sorting pass; -1 for the self entry gcn adds to a row without a self loop
+ * (under gcn a row's own self entry is the source of its transposed self
+ * entry).  It turns per-edge weights in forward order into transposed order,
+ * so weights can be replaced without rebuilding a plan. */
+enum { GS_FP_T_ROW_PTR = 8, GS_FP_T_COL = 9, GS_FP_T_SRC = 10 };
 int gs_full_plan_transpose(const gs_full_plan* plan, const int64_t* row_ptr, const int32_t* col,
                            int64_t seg_len, gs_full_plan** out);
 

@@ -5,7 +5,8 @@
 // planned at several seg_len with gcn on and off; every plan is recounted
 // here (items cover each row once, in order; counts, flags, empty rows), its
 // transposed plan (gs_full_plan_transpose; the CSR is directed) is checked
-// entry by entry, and the error paths are taken.
+// entry by entry with its T_SRC array, the weighted mean's divisors
+// (gs_full_plan_edge_denom) are recomputed, and the error paths are taken.
 //   make -C graphsage-pytorch_amd/csrc sanitize-full-plan
 // builds it with the host sources under -fsanitize=address,undefined (the
 // Makefile's ASANFLAGS) and runs it once; it prints one line and exits 0.
@@ -120,6 +121,8 @@ int main() {
             const int32_t* tcol = arr<int32_t>(t, GS_FP_T_COL);
             const int32_t* tcnt = arr<int32_t>(t, GS_FP_COUNT);
             const int64_t* titem_ptr = arr<int64_t>(t, GS_FP_ITEM_PTR);
+            const int64_t* tsrc = arr<int64_t>(t, GS_FP_T_SRC);
+            CHECK(tsrc != nullptr && arr<int64_t>(p, GS_FP_T_SRC) == nullptr);
             CHECK(arr<int64_t>(p, GS_FP_T_ROW_PTR) == nullptr && arr<int32_t>(p, GS_FP_T_COL) == nullptr);
             int64_t kept = 0;
             for (int64_t v = 0; v < n; ++v) {
@@ -136,10 +139,28 @@ int main() {
                     const int32_t v = tcol[e];
                     CHECK(v >= 0 && v < n && (e == trp[u] || tcol[e - 1] <= v));
                     own += v == u;
+                    // T_SRC: the forward entry behind this one, in v's row and naming u; -1: the self entry gcn added
+                    const int64_t src = tsrc[e];
+                    if (src < 0) CHECK(gcn && v == u && !self_loop[u]);
+                    else CHECK(src >= row_ptr[v] && src < row_ptr[v + 1] && col[src] == u);
                     CHECK(v == u || std::find(rows[v].begin(), rows[v].end(), static_cast<int32_t>(u)) != rows[v].end());
                 }
                 CHECK(own == gcn);
             }
+            // the weighted mean's divisor: the double sum of a row's effective weights, rounded once
+            std::vector<float> w(col.size()), sw(n), den(n, -1.f);
+            for (size_t e = 0; e < w.size(); ++e) w[e] = 0.25f + static_cast<float>(next_u64() % 1000) / 256.f;
+            for (int64_t v = 0; v < n; ++v) sw[v] = 0.5f + static_cast<float>(v % 7);
+            CHECK(gs_full_plan_edge_denom(p, row_ptr.data(), col.data(), w.data(), sw.data(), den.data()) == GS_OK);
+            for (int64_t v = 0; v < n; ++v) {
+                double sum = 0.0;
+                for (int64_t e = row_ptr[v]; e < row_ptr[v + 1]; ++e)
+                    if (gcn || col[e] != v) sum += w[e];
+                if (gcn && !self_loop[v]) sum += sw[v];
+                CHECK(den[v] == static_cast<float>(sum));
+            }
+            CHECK(gs_full_plan_edge_denom(t, trp, tcol, w.data(), nullptr, den.data()) == GS_EINVAL);  // transposed
+            CHECK(gs_full_plan_edge_denom(p, row_ptr.data(), col.data(), w.data(), nullptr, nullptr) == GS_EINVAL);
             gs_full_plan* tt = nullptr;
             CHECK(gs_full_plan_transpose(t, trp, tcol, seg_len, &tt) == GS_EINVAL);  // already transposed
             CHECK(gs_full_plan_transpose(p, row_ptr.data(), col.data(), seg_len, nullptr) == GS_EINVAL);
